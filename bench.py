@@ -18,7 +18,21 @@ Modes:
                    --trainer and 8 ranks (reference:
                    example/qwen3_moe/pretrain.json)
 
+A plain run sets up, warms up, times the steps and prints the result line;
+that is all the headline figure needs, and today the benchmark measures
+nothing else. --full is where any extra measurement (baselines, other
+precisions or sizes, reference comparisons, per-kernel figures) belongs.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step
+computed (rank 0's view) as float32 DIR/<name>.npy:
+  loss           per-microbatch loss
+  logps          per-token log p(label) of every microbatch (raw loop)
+  params_sample  a fixed seeded sample of every updated parameter
+  grads_sample   the same sample of the accumulated gradients (raw loop)
+Seeds are fixed, so the same arguments give the same inputs on every run.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--trainer]
+                       [--dump-outputs DIR] [--full]
 Driver contract: one JSON line from rank 0 with the whole-job tokens/sec.
 """
 
@@ -53,7 +67,50 @@ def parse_args():
              "dispatch); ref = the reference example mesh PP4xDPR2xEP2 "
              "looped_bfs (needs --trainer and 8 ranks)",
     )
-    return p.parse_args()
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the last timed step's outputs as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure "
+                        "(none exist today; a plain run never does them)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
+
+
+_SAMPLE_PER_TENSOR = 8192  # ~170 tensors x 8192 x 4 B = ~5.5 MB per dump file
+
+
+def sample_tensors(named_tensors):
+    """A fixed seeded sample of every tensor, concatenated, as float32 on CPU.
+
+    Tensors of up to _SAMPLE_PER_TENSOR elements are taken whole; the indices
+    depend only on the tensor's position and size, never on the data.
+    """
+    from torch.distributed.tensor import DTensor
+
+    parts = []
+    for i, (_, t) in enumerate(named_tensors):
+        if t is None:
+            continue
+        t = (t.to_local() if isinstance(t, DTensor) else t).detach().reshape(-1)
+        if t.numel() > _SAMPLE_PER_TENSOR:
+            g = torch.Generator().manual_seed(0xD9D + i)
+            idx = torch.randint(0, t.numel(), (_SAMPLE_PER_TENSOR,), generator=g)
+            t = t[idx.to(t.device)]
+        parts.append(t.float().cpu())
+    return torch.cat(parts) if parts else torch.zeros(0)
+
+
+def dump_outputs(directory, outputs):
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, value in outputs.items():
+        arr = torch.as_tensor(value).detach().float().cpu().numpy()
+        np.save(os.path.join(directory, f"{name}.npy"), arr.astype(np.float32))
 
 
 def model_flops_per_token(params, seq_len: int) -> float:
@@ -127,17 +184,20 @@ def run_raw(args, params, rank, world, local_rank, device, distributed):
     ]
 
     inv_world = 1.0 / world
+    last_outputs = []  # (loss, logps) per microbatch of the latest step
 
     def one_step():
         if sync is not None:
             sync.zero_grad()
         opt.zero_grad(set_to_none=False)
+        last_outputs.clear()
         for mb in range(n_micro):
             data = batches[mb % len(batches)]
             input_ids = data[:, :-1]
             labels = data[:, 1:]
             out = model(input_ids=input_ids, labels=labels)
             (out["loss"].mean() / n_micro).backward()
+            last_outputs.append((out["loss"].detach(), out["logps"].detach()))
         if sync is not None:
             # bucketed all-reduce launched by post-accumulate hooks on a side
             # stream, overlapped with backward; join + average here
@@ -152,8 +212,17 @@ def run_raw(args, params, rank, world, local_rank, device, distributed):
             torch._foreach_mul_(grads, inv_world)
         opt.step()
 
+    def collect():
+        named = list(model.named_parameters())
+        return {
+            "loss": torch.cat([l.reshape(-1) for l, _ in last_outputs]),
+            "logps": torch.stack([lp for _, lp in last_outputs]),
+            "params_sample": sample_tensors(named),
+            "grads_sample": sample_tensors([(n, p.grad) for n, p in named]),
+        }
+
     tokens_per_step = B * S * n_micro * world
-    return one_step, tokens_per_step, f"dp{world}" if args.parallelism == "dp" else f"dp{world}+ep{world}", "weak"
+    return one_step, tokens_per_step, f"dp{world}" if args.parallelism == "dp" else f"dp{world}+ep{world}", "weak", collect
 
 
 def run_trainer(args, params, rank, world, local_rank, device, distributed):
@@ -274,8 +343,21 @@ def run_trainer(args, params, rank, world, local_rank, device, distributed):
     def one_step():
         trainer._train_step(batch)
 
+    def collect():
+        # the Trainer zeroes the gradients at the end of its step, so the
+        # step's results are the losses and the updated parameters
+        named = [
+            (f"{i}.{n}", p)
+            for i, m in enumerate(trainer.schedule_info.modules)
+            for n, p in m.named_parameters()
+        ]
+        return {
+            "loss": torch.tensor(trainer.last_losses, dtype=torch.float32),
+            "params_sample": sample_tensors(named),
+        }
+
     tokens_per_step = global_batch * S
-    return one_step, tokens_per_step, parallelism_tag, scaling
+    return one_step, tokens_per_step, parallelism_tag, scaling, collect
 
 
 def main():
@@ -312,12 +394,12 @@ def main():
     )
 
     if args.trainer or args.parallelism == "ref":
-        one_step, tokens_per_step, parallelism_tag, scaling = run_trainer(
+        one_step, tokens_per_step, parallelism_tag, scaling, collect = run_trainer(
             args, params, rank, world, local_rank, device, distributed
         )
         engine = "trainer"
     else:
-        one_step, tokens_per_step, parallelism_tag, scaling = run_raw(
+        one_step, tokens_per_step, parallelism_tag, scaling, collect = run_raw(
             args, params, rank, world, local_rank, device, distributed
         )
         engine = "raw"
@@ -344,6 +426,9 @@ def main():
         t = torch.tensor([elapsed], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, collect())
 
     ms_per_step = elapsed / args.steps * 1000
     total_tokens = tokens_per_step * args.steps

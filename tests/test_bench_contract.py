@@ -55,6 +55,36 @@ def test_bench_trainer_json_contract():
     assert rec["value"] > 0
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32 .npy;
+    the same arguments give the same inputs, so on CPU two runs agree exactly.
+    --steps sets the number of timed steps, and --full is accepted."""
+    import numpy as np
+
+    recs, dumps = [], []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / tag
+        recs.append(_run_bench(["--steps", "2", "--dump-outputs", str(d)] + extra))
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    assert recs[0]["steps"] == 2 and recs[0]["ms_per_step"] > 0
+    assert set(dumps[0]) == {"loss", "logps", "params_sample", "grads_sample"}
+    assert dumps[0]["loss"].shape == (2,)  # one per microbatch (--grad-accum 2)
+    assert dumps[0]["logps"].shape == (2, 2, 32)
+    assert dumps[0]["params_sample"].shape == dumps[0]["grads_sample"].shape
+    total = 0
+    for name, arr in dumps[0].items():
+        assert arr.dtype == np.float32 and np.isfinite(arr).all(), name
+        assert np.array_equal(arr, dumps[1][name]), name
+        total += arr.nbytes
+    assert total <= 64 * 2**20
+    # the loss of a microbatch is the mean of its tokens' -log p(label);
+    # both are bf16 values (2^-8 relative rounding each), hence 1e-2
+    np.testing.assert_allclose(
+        dumps[0]["loss"], -dumps[0]["logps"].mean(axis=(1, 2)), rtol=1e-2
+    )
+    assert np.abs(dumps[0]["grads_sample"]).max() > 0
+
+
 @pytest.mark.slow
 def test_bench_trainer_ref_mesh_ws8():
     rec = _run_bench(["--trainer", "--parallelism", "ref", "--gpus", "8"], nproc=8)
