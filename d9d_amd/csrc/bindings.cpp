@@ -51,6 +51,23 @@ std::vector<torch::Tensor> gdn_chunk_bwd_scan(torch::Tensor q, torch::Tensor k,
                                               torch::Tensor dout,
                                               torch::Tensor beta,
                                               torch::Tensor decay_log);
+// packed-document (cu_seqlens) variants of the four entry points above
+torch::Tensor causal_conv_silu_varlen_fwd(torch::Tensor x, torch::Tensor w,
+                                          torch::Tensor cu_seqlens);
+std::vector<torch::Tensor> causal_conv_silu_varlen_bwd(torch::Tensor x, torch::Tensor w,
+                                                       torch::Tensor dy,
+                                                       torch::Tensor cu_seqlens);
+std::vector<torch::Tensor> gdn_chunk_fwd_varlen(torch::Tensor q, torch::Tensor k,
+                                                torch::Tensor v, torch::Tensor beta,
+                                                torch::Tensor decay_log,
+                                                torch::Tensor cu_seqlens,
+                                                bool return_state, bool return_aux,
+                                                bool skip_out);
+std::vector<torch::Tensor> gdn_chunk_bwd_scan_varlen(torch::Tensor q, torch::Tensor k,
+                                                     torch::Tensor dout,
+                                                     torch::Tensor beta,
+                                                     torch::Tensor decay_log,
+                                                     torch::Tensor cu_seqlens);
 
 torch::Tensor cce_dlogits_(torch::Tensor logits, torch::Tensor lse, torch::Tensor targets,
                            torch::Tensor dl, c10::optional<torch::Tensor> dlse,
@@ -90,6 +107,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gdn_chunk_fwd", &gdn_chunk_fwd, "chunked gated delta rule forward (GDN)");
   m.def("gdn_chunk_bwd_scan", &gdn_chunk_bwd_scan,
         "chunked gated delta rule backward reverse scan (GDN)");
+  m.def("causal_conv_silu_varlen_fwd", &causal_conv_silu_varlen_fwd,
+        "fused causal depthwise conv + SiLU fwd, packed documents");
+  m.def("causal_conv_silu_varlen_bwd", &causal_conv_silu_varlen_bwd,
+        "fused causal depthwise conv + SiLU bwd, packed documents");
+  m.def("gdn_chunk_fwd_varlen", &gdn_chunk_fwd_varlen,
+        "chunked gated delta rule forward, packed documents (GDN)");
+  m.def("gdn_chunk_bwd_scan_varlen", &gdn_chunk_bwd_scan_varlen,
+        "chunked gated delta rule backward reverse scan, packed documents (GDN)");
   m.def("adamw_stochastic_bf16_multi_", &adamw_stochastic_bf16_multi_, "multi-tensor fused SR-AdamW");
   m.def("gmm", &gmm, "CDNA4 grouped GEMM (MoE experts)");
   m.def("gmm_nt", &gmm_nt, "CDNA4 grouped GEMM, weight (E,N,K)");

@@ -11,6 +11,10 @@
 //    unit-lower triangular solve. Dk = Dv = 64.
 //    (The python wrapper pairs this forward with a recompute-through-the
 //    torch-WY-graph backward; a native bwd kernel is the follow-up.)
+// 3. Packed-document (cu_seqlens) variants of all four entry points: the
+//    same kernel bodies under a VARLEN template flag — one workgroup per
+//    (document, head) from a zero state, conv taps clipped at the
+//    document start. cu_seqlens is validated on the host before launch.
 #include "common.h"
 
 #include <torch/extension.h>
@@ -29,11 +33,31 @@ D9D_DEVICE f32x4 mfma16gdn(bf16x8 a, bf16x8 b, f32x4 c) {
 // ---------------------------------------------------------------------------
 // causal depthwise conv (kernel <= 4) + SiLU, bf16
 // ---------------------------------------------------------------------------
+//
+// VARLEN: x is one packed row of documents (B == 1) and cu (nseq+1 int32,
+// host-validated: cu[0] = 0, non-decreasing, cu[nseq] = S) bounds them; a
+// tap is taken only inside the document that row s belongs to. Dense is the
+// same code with the document being the whole row [0, S).
 
+// Document [lo, hi) holding packed row s: the last i with cu[i] <= s (empty
+// documents repeat an entry; the last repeat is the non-empty one).
+D9D_DEVICE void conv_doc_bounds(const int* __restrict__ cu, int nseq,
+                                int64_t s, int64_t& lo, int64_t& hi) {
+  int a = 0, b = nseq - 1;
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if ((int64_t)cu[mid] <= s) a = mid; else b = mid - 1;
+  }
+  lo = cu[a];
+  hi = cu[a + 1];
+}
+
+template <bool VARLEN>
 __global__ void causal_conv_silu_fwd_kernel(
     const bf16_t* __restrict__ x,   // (B, S, C)
     const bf16_t* __restrict__ w,   // (C, K)
     bf16_t* __restrict__ out,       // (B, S, C)
+    const int* __restrict__ cu, int nseq,
     int64_t B, int64_t S, int64_t C, int K) {
   const int64_t total = B * S * C;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -41,11 +65,14 @@ __global__ void causal_conv_silu_fwd_kernel(
     const int64_t c = i % C;
     const int64_t s = (i / C) % S;
     const int64_t b = i / (C * S);
+    int64_t lo = 0, hi = S;
+    if constexpr (VARLEN) conv_doc_bounds(cu, nseq, s, lo, hi);
+    (void)hi;
     float acc = 0.f;
 #pragma unroll 4
     for (int t = 0; t < K; ++t) {
       const int64_t sp = s - (K - 1 - t);
-      if (sp >= 0) {
+      if (sp >= lo) {
         acc += (float)x[(b * S + sp) * C + c] * (float)w[c * K + t];
       }
     }
@@ -56,12 +83,14 @@ __global__ void causal_conv_silu_fwd_kernel(
 
 // dx and dw for conv+silu. dpre = dy * silu'(pre); dx[s] = sum_t dpre[s+K-1-t]*w[t]
 // (within bounds); dw[c,t] = sum_{b,s} dpre[b,s,c] * x[b, s-(K-1-t), c].
+template <bool VARLEN>
 __global__ void causal_conv_silu_bwd_kernel(
     const bf16_t* __restrict__ x,
     const bf16_t* __restrict__ w,
     const bf16_t* __restrict__ dy,
     bf16_t* __restrict__ dx,        // (B, S, C)
     float* __restrict__ dw,         // (C, K) fp32 (atomic)
+    const int* __restrict__ cu, int nseq,
     int64_t B, int64_t S, int64_t C, int K) {
   const int64_t total = B * S * C;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -69,6 +98,10 @@ __global__ void causal_conv_silu_bwd_kernel(
     const int64_t c = i % C;
     const int64_t s = (i / C) % S;
     const int64_t b = i / (C * S);
+    // every row this thread touches (s-K+1 .. s+K-1, clipped) is in s's
+    // document, so one lookup serves the dx, dw and recompute taps
+    int64_t lo = 0, hi = S;
+    if constexpr (VARLEN) conv_doc_bounds(cu, nseq, s, lo, hi);
 
     // recompute pre-activation at s (cheap: K<=4 reads)
     auto pre_at = [&](int64_t sq) -> float {
@@ -76,7 +109,7 @@ __global__ void causal_conv_silu_bwd_kernel(
 #pragma unroll 4
       for (int t = 0; t < K; ++t) {
         const int64_t sp = sq - (K - 1 - t);
-        if (sp >= 0) acc += (float)x[(b * S + sp) * C + c] * (float)w[c * K + t];
+        if (sp >= lo) acc += (float)x[(b * S + sp) * C + c] * (float)w[c * K + t];
       }
       return acc;
     };
@@ -90,7 +123,7 @@ __global__ void causal_conv_silu_bwd_kernel(
 #pragma unroll 4
     for (int t = 0; t < K; ++t) {
       const int64_t sq = s + (K - 1 - t);
-      if (sq < S) {
+      if (sq < hi) {
         const float dpre = (float)dy[(b * S + sq) * C + c] * dsilu(pre_at(sq));
         acc_dx += dpre * (float)w[c * K + t];
       }
@@ -102,7 +135,7 @@ __global__ void causal_conv_silu_bwd_kernel(
 #pragma unroll 4
     for (int t = 0; t < K; ++t) {
       const int64_t sp = s - (K - 1 - t);
-      if (sp >= 0) {
+      if (sp >= lo) {
         atomicAdd(&dw[c * K + t], dpre_s * (float)x[(b * S + sp) * C + c]);
       }
     }
@@ -156,7 +189,42 @@ struct GdnLds {
   float beta[kGdnC];
 };
 
-template <int DVT>
+// What one workgroup walks: `len` rows starting at flat row `row0` of the
+// (B*H*S) row space, whose chunks are numbered from `chunk0` in the
+// (B*H*nc) chunk space.
+//   dense : workgroup = (b, h); the whole sequence, row0 = bh*S.
+//   varlen: workgroup = (document, head) of ONE packed row (B == 1, S = T
+//           packed tokens); the document's rows only, chunks local to the
+//           document and numbered after those of the documents before it
+//           (chunk_off, nc_total = chunk_off[nseq]). cu / chunk_off are
+//           host-validated: cu[0] = 0, non-decreasing, cu[nseq] = S.
+struct GdnSpan {
+  int64_t row0;
+  int64_t chunk0;
+  int64_t len;
+};
+
+template <bool VARLEN>
+D9D_DEVICE GdnSpan gdn_span(int64_t wg, int64_t S, const int* __restrict__ cu,
+                            const int* __restrict__ chunk_off, int H,
+                            int64_t nc_total) {
+  GdnSpan sp;
+  if constexpr (VARLEN) {
+    const int64_t doc = wg / H;
+    const int64_t h = wg % H;
+    const int64_t start = cu[doc];
+    sp.row0 = h * S + start;
+    sp.chunk0 = h * nc_total + chunk_off[doc];
+    sp.len = (int64_t)cu[doc + 1] - start;
+  } else {
+    sp.row0 = wg * S;
+    sp.chunk0 = wg * ((S + kGdnC - 1) / kGdnC);
+    sp.len = S;
+  }
+  return sp;
+}
+
+template <int DVT, bool VARLEN>
 __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
     const bf16_t* __restrict__ q,   // (B, H, S, D)
     const bf16_t* __restrict__ k,
@@ -164,10 +232,13 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
     const float* __restrict__ beta,      // (B, H, S)
     const float* __restrict__ decay_log, // (B, H, S)
     bf16_t* __restrict__ out,            // (B, H, S, D)
-    float* __restrict__ final_state,     // (B, H, D, D) or nullptr
+    float* __restrict__ final_state,     // (n_wg, D, D) or nullptr
     float* __restrict__ r_out,           // (B, H, S, D) fp32 or nullptr
     float* __restrict__ s0_out,          // (B, H, nc, D, D) fp32 or nullptr
-    int64_t BH, int64_t S) {
+    int64_t n_wg, int64_t S,
+    const int* __restrict__ cu,          // varlen only
+    const int* __restrict__ chunk_off,   // varlen only
+    int H, int64_t nc_total) {           // varlen only
   constexpr int NTV = DVT / 16;        // v tiles per wave quarter
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   GdnLds<DVT>& L = *reinterpret_cast<GdnLds<DVT>*>(smem_raw);
@@ -176,14 +247,16 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
   const int wave = threadIdx.x >> 6;   // 4 waves; wave w owns m-rows 16w..16w+15
   const int64_t bh = blockIdx.x;
   const int v0 = blockIdx.y * DVT;     // this block's Dv slice
-  if (bh >= BH) return;
+  if (bh >= n_wg) return;
 
-  const bf16_t* qp = q + bh * S * kGdnD;
-  const bf16_t* kp = k + bh * S * kGdnD;
-  const bf16_t* vp = v + bh * S * kGdnD;
-  const float* bp = beta + bh * S;
-  const float* gp = decay_log + bh * S;
-  bf16_t* op = out + bh * S * kGdnD;
+  const GdnSpan span = gdn_span<VARLEN>(bh, S, cu, chunk_off, H, nc_total);
+  const int64_t len = span.len;
+  const bf16_t* qp = q + span.row0 * kGdnD;
+  const bf16_t* kp = k + span.row0 * kGdnD;
+  const bf16_t* vp = v + span.row0 * kGdnD;
+  const float* bp = beta + span.row0;
+  const float* gp = decay_log + span.row0;
+  bf16_t* op = out + span.row0 * kGdnD;
 
   for (int i = threadIdx.x; i < kGdnD * DVT; i += 256) {
     (&L.state[0][0])[i] = 0.f;
@@ -191,10 +264,10 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
   __syncthreads();
 
   const float kLog2eG = 1.44269504f;
-  const int n_chunks = (int)((S + kGdnC - 1) / kGdnC);
+  const int n_chunks = (int)((len + kGdnC - 1) / kGdnC);
   for (int ch = 0; ch < n_chunks; ++ch) {
     const int s0 = ch * kGdnC;
-    const int c_rows = min((int)(S - (int64_t)s0), kGdnC);
+    const int c_rows = min((int)(len - (int64_t)s0), kGdnC);
 
     // ---- stage chunk tiles (zero-pad past c_rows) + state^T bf16 -------
     for (int i = threadIdx.x; i < kGdnC * kGdnD / 8; i += 256) {
@@ -240,7 +313,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
     __syncthreads();
 
     if (s0_out != nullptr) {
-      float* sp = s0_out + (bh * n_chunks + ch) * (int64_t)kGdnD * kGdnD;
+      float* sp = s0_out + (span.chunk0 + ch) * (int64_t)kGdnD * kGdnD;
       for (int i = threadIdx.x; i < kGdnD * DVT; i += 256) {
         const int dk = i / DVT;
         const int dv = i % DVT;
@@ -363,7 +436,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
         const int t = i / DVT;
         const int dv = i % DVT;
         if (t < c_rows) {
-          r_out[(bh * S + s0 + t) * kGdnD + v0 + dv] = L.R[t][dv];
+          r_out[(span.row0 + s0 + t) * kGdnD + v0 + dv] = L.R[t][dv];
         }
       }
     }
@@ -531,7 +604,7 @@ struct GdnBwdLds {
   float beta[kGdnC];
 };
 
-template <int DVT>
+template <int DVT, bool VARLEN>
 __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
     const bf16_t* __restrict__ q,    // (B, H, S, D)
     const bf16_t* __restrict__ k,
@@ -540,7 +613,10 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
     const float* __restrict__ decay_log,
     float* __restrict__ drhs_out,    // (B, H, S, D)
     float* __restrict__ ds0_out,     // (B, H, nc, D, D)
-    int64_t BH, int64_t S) {
+    int64_t n_wg, int64_t S,
+    const int* __restrict__ cu,          // varlen only (see GdnSpan)
+    const int* __restrict__ chunk_off,   // varlen only
+    int H, int64_t nc_total) {           // varlen only
   constexpr int NTV = DVT / 16;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   GdnBwdLds<DVT>& L = *reinterpret_cast<GdnBwdLds<DVT>*>(smem_raw);
@@ -549,13 +625,15 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
   const int wave = threadIdx.x >> 6;
   const int64_t bh = blockIdx.x;
   const int v0 = blockIdx.y * DVT;
-  if (bh >= BH) return;
+  if (bh >= n_wg) return;
 
-  const bf16_t* qp = q + bh * S * kGdnD;
-  const bf16_t* kp = k + bh * S * kGdnD;
-  const bf16_t* dop = dout + bh * S * kGdnD;
-  const float* bp = beta + bh * S;
-  const float* gp = decay_log + bh * S;
+  const GdnSpan span = gdn_span<VARLEN>(bh, S, cu, chunk_off, H, nc_total);
+  const int64_t len = span.len;
+  const bf16_t* qp = q + span.row0 * kGdnD;
+  const bf16_t* kp = k + span.row0 * kGdnD;
+  const bf16_t* dop = dout + span.row0 * kGdnD;
+  const float* bp = beta + span.row0;
+  const float* gp = decay_log + span.row0;
 
   for (int i = threadIdx.x; i < kGdnD * DVT; i += 256) {
     (&L.dS[0][0])[i] = 0.f;
@@ -563,10 +641,10 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
   __syncthreads();
 
   const float kLog2eG = 1.44269504f;
-  const int n_chunks = (int)((S + kGdnC - 1) / kGdnC);
+  const int n_chunks = (int)((len + kGdnC - 1) / kGdnC);
   for (int ch = n_chunks - 1; ch >= 0; --ch) {
     const int s0 = ch * kGdnC;
-    const int c_rows = min((int)(S - (int64_t)s0), kGdnC);
+    const int c_rows = min((int)(len - (int64_t)s0), kGdnC);
 
     // ---- stage chunk tiles (zero-pad), dS^T, decay scan ----------------
     for (int i = threadIdx.x; i < kGdnC * kGdnD / 8; i += 256) {
@@ -740,7 +818,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
       const int t = i / DVT;
       const int dv = i % DVT;
       if (t < c_rows) {
-        drhs_out[(bh * S + s0 + t) * kGdnD + v0 + dv] = L.dx[t][dv];
+        drhs_out[(span.row0 + s0 + t) * kGdnD + v0 + dv] = L.dx[t][dv];
       }
     }
 
@@ -790,7 +868,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
           acc += (float)L.ks[t][dk] * (float)L.doc[t][dv];
         }
         L.dS[dk][dv] = acc;
-        ds0_out[(bh * n_chunks + ch) * (int64_t)kGdnD * kGdnD +
+        ds0_out[(span.chunk0 + ch) * (int64_t)kGdnD * kGdnD +
                 dk * kGdnD + v0 + dv] = acc;
       }
     }
@@ -804,27 +882,78 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
 // host wrappers
 // ---------------------------------------------------------------------------
 
-torch::Tensor causal_conv_silu_fwd(torch::Tensor x, torch::Tensor w) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(w.size(1) <= 4, "conv kernel must be <= 4");
+namespace {
+
+// Packed-document boundaries, checked on the host BEFORE anything is
+// launched: the kernels index global memory straight from these values, so
+// a bad cu_seqlens must never reach them. The CPU copy also sizes the grid
+// (as flash_attn_fwd does for its varlen path).
+struct GdnDocs {
+  torch::Tensor cu_dev;         // (nseq+1,) int32 on the device
+  torch::Tensor chunk_off_dev;  // (nseq+1,) int32: 64-row chunks before doc i
+  int64_t nseq = 0;
+  int64_t nc = 0;               // chunk_off[nseq]
+};
+
+GdnDocs gdn_check_docs(const torch::Tensor& cu_seqlens, int64_t batch,
+                       int64_t T, const torch::Device& dev, bool with_chunks) {
+  TORCH_CHECK(batch == 1, "packed cu_seqlens input expects batch dim 1, got ",
+              batch);
+  TORCH_CHECK(cu_seqlens.scalar_type() == torch::kInt32,
+              "cu_seqlens must be int32");
+  TORCH_CHECK(cu_seqlens.dim() == 1 && cu_seqlens.numel() >= 2,
+              "cu_seqlens must be (nseq+1,) with nseq >= 1");
+  auto cu_cpu = cu_seqlens.cpu().contiguous();
+  const int* cu = cu_cpu.data_ptr<int>();
+  GdnDocs d;
+  d.nseq = cu_cpu.numel() - 1;
+  TORCH_CHECK(cu[0] == 0, "cu_seqlens[0] must be 0, got ", cu[0]);
+  for (int64_t i = 0; i < d.nseq; ++i) {
+    TORCH_CHECK(cu[i + 1] >= cu[i], "cu_seqlens decreases at entry ", i + 1);
+  }
+  TORCH_CHECK((int64_t)cu[d.nseq] == T, "cu_seqlens[-1] = ", cu[d.nseq],
+              " does not match the ", T, " packed rows");
+  d.cu_dev = (cu_seqlens.device() == dev) ? cu_seqlens.contiguous()
+                                            : cu_cpu.to(dev);
+  if (with_chunks) {
+    auto off = torch::empty({d.nseq + 1}, torch::dtype(torch::kInt32));
+    int* p = off.data_ptr<int>();
+    int total = 0;
+    for (int64_t i = 0; i < d.nseq; ++i) {
+      p[i] = total;
+      total += (cu[i + 1] - cu[i] + d9d::kGdnC - 1) / d9d::kGdnC;
+    }
+    p[d.nseq] = total;
+    d.nc = total;
+    d.chunk_off_dev = off.to(dev);
+  }
+  return d;
+}
+
+template <bool VARLEN>
+torch::Tensor conv_silu_fwd_impl(const torch::Tensor& x, const torch::Tensor& w,
+                                 const int* cu, int nseq) {
   auto xc = x.contiguous();
   auto wc = w.contiguous();
   auto out = torch::empty_like(xc);
   const int64_t B = xc.size(0), S = xc.size(1), C = xc.size(2);
   const int64_t total = B * S * C;
+  if (total == 0) return out;
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
   auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(d9d::causal_conv_silu_fwd_kernel, dim3(blocks), dim3(256),
-                     0, stream,
+  hipLaunchKernelGGL(d9d::causal_conv_silu_fwd_kernel<VARLEN>, dim3(blocks),
+                     dim3(256), 0, stream,
                      reinterpret_cast<const __bf16*>(xc.data_ptr()),
                      reinterpret_cast<const __bf16*>(wc.data_ptr()),
                      reinterpret_cast<__bf16*>(out.data_ptr()),
-                     B, S, C, (int)w.size(1));
+                     cu, nseq, B, S, C, (int)w.size(1));
   return out;
 }
 
-std::vector<torch::Tensor> causal_conv_silu_bwd(
-    torch::Tensor x, torch::Tensor w, torch::Tensor dy) {
+template <bool VARLEN>
+std::vector<torch::Tensor> conv_silu_bwd_impl(
+    const torch::Tensor& x, const torch::Tensor& w, const torch::Tensor& dy,
+    const int* cu, int nseq) {
   auto xc = x.contiguous();
   auto wc = w.contiguous();
   auto dyc = dy.contiguous();
@@ -834,16 +963,165 @@ std::vector<torch::Tensor> causal_conv_silu_bwd(
       torch::dtype(torch::kFloat32).device(w.device()));
   const int64_t B = xc.size(0), S = xc.size(1), C = xc.size(2);
   const int64_t total = B * S * C;
+  if (total == 0) return {dx, dw.to(w.scalar_type())};
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
   auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(d9d::causal_conv_silu_bwd_kernel, dim3(blocks), dim3(256),
-                     0, stream,
+  hipLaunchKernelGGL(d9d::causal_conv_silu_bwd_kernel<VARLEN>, dim3(blocks),
+                     dim3(256), 0, stream,
                      reinterpret_cast<const __bf16*>(xc.data_ptr()),
                      reinterpret_cast<const __bf16*>(wc.data_ptr()),
                      reinterpret_cast<const __bf16*>(dyc.data_ptr()),
                      reinterpret_cast<__bf16*>(dx.data_ptr()),
-                     dw.data_ptr<float>(), B, S, C, (int)w.size(1));
+                     dw.data_ptr<float>(), cu, nseq, B, S, C, (int)w.size(1));
   return {dx, dw.to(w.scalar_type())};
+}
+
+void conv_varlen_checks(const torch::Tensor& x, const torch::Tensor& w) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(x.dim() == 3 && w.dim() == 2 && w.size(0) == x.size(2),
+              "expected x (1, T, C) and w (C, K)");
+  TORCH_CHECK(w.size(1) <= 4, "conv kernel must be <= 4");
+}
+
+// Dv-split rule shared by every chunk launch: below ~1.5 workgroups/CU the
+// duplicated K-side work is cheaper than idle CUs.
+bool gdn_split_dv(int64_t n_wg) { return n_wg * 2 <= 384; }
+
+template <bool VARLEN>
+void gdn_fwd_launch(int64_t n_wg, int64_t S, const torch::Tensor& q,
+                    const torch::Tensor& k, const torch::Tensor& v,
+                    const torch::Tensor& beta, const torch::Tensor& g,
+                    __bf16* out, float* fs, float* r, float* s0,
+                    const int* cu, const int* chunk_off, int H, int64_t nc) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&d9d::gdn_chunk_fwd_kernel<64, VARLEN>),
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)sizeof(d9d::GdnLds<64>));
+    hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&d9d::gdn_chunk_fwd_kernel<32, VARLEN>),
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)sizeof(d9d::GdnLds<32>));
+    attr_set = true;
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  if (gdn_split_dv(n_wg)) {
+    hipLaunchKernelGGL((d9d::gdn_chunk_fwd_kernel<32, VARLEN>),
+                       dim3((unsigned)n_wg, 2), dim3(256),
+                       sizeof(d9d::GdnLds<32>), stream,
+                       reinterpret_cast<const __bf16*>(q.data_ptr()),
+                       reinterpret_cast<const __bf16*>(k.data_ptr()),
+                       reinterpret_cast<const __bf16*>(v.data_ptr()),
+                       beta.data_ptr<float>(), g.data_ptr<float>(),
+                       out, fs, r, s0, n_wg, S, cu, chunk_off, H, nc);
+  } else {
+    hipLaunchKernelGGL((d9d::gdn_chunk_fwd_kernel<64, VARLEN>),
+                       dim3((unsigned)n_wg, 1), dim3(256),
+                       sizeof(d9d::GdnLds<64>), stream,
+                       reinterpret_cast<const __bf16*>(q.data_ptr()),
+                       reinterpret_cast<const __bf16*>(k.data_ptr()),
+                       reinterpret_cast<const __bf16*>(v.data_ptr()),
+                       beta.data_ptr<float>(), g.data_ptr<float>(),
+                       out, fs, r, s0, n_wg, S, cu, chunk_off, H, nc);
+  }
+}
+
+template <bool VARLEN>
+void gdn_bwd_scan_launch(int64_t n_wg, int64_t S, const torch::Tensor& q,
+                         const torch::Tensor& k, const torch::Tensor& dout,
+                         const torch::Tensor& beta, const torch::Tensor& g,
+                         float* drhs, float* ds0, const int* cu,
+                         const int* chunk_off, int H, int64_t nc) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute(
+        reinterpret_cast<const void*>(
+            &d9d::gdn_chunk_bwd_scan_kernel<64, VARLEN>),
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)sizeof(d9d::GdnBwdLds<64>));
+    hipFuncSetAttribute(
+        reinterpret_cast<const void*>(
+            &d9d::gdn_chunk_bwd_scan_kernel<32, VARLEN>),
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)sizeof(d9d::GdnBwdLds<32>));
+    attr_set = true;
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  // same Dv-split heuristic as the forward kernel
+  if (gdn_split_dv(n_wg)) {
+    hipLaunchKernelGGL((d9d::gdn_chunk_bwd_scan_kernel<32, VARLEN>),
+                       dim3((unsigned)n_wg, 2), dim3(256),
+                       sizeof(d9d::GdnBwdLds<32>), stream,
+                       reinterpret_cast<const __bf16*>(q.data_ptr()),
+                       reinterpret_cast<const __bf16*>(k.data_ptr()),
+                       reinterpret_cast<const __bf16*>(dout.data_ptr()),
+                       beta.data_ptr<float>(), g.data_ptr<float>(),
+                       drhs, ds0, n_wg, S, cu, chunk_off, H, nc);
+  } else {
+    hipLaunchKernelGGL((d9d::gdn_chunk_bwd_scan_kernel<64, VARLEN>),
+                       dim3((unsigned)n_wg, 1), dim3(256),
+                       sizeof(d9d::GdnBwdLds<64>), stream,
+                       reinterpret_cast<const __bf16*>(q.data_ptr()),
+                       reinterpret_cast<const __bf16*>(k.data_ptr()),
+                       reinterpret_cast<const __bf16*>(dout.data_ptr()),
+                       beta.data_ptr<float>(), g.data_ptr<float>(),
+                       drhs, ds0, n_wg, S, cu, chunk_off, H, nc);
+  }
+}
+
+// (1, H, T, 64) bf16 rows + (1, H, T) gates of one packed row
+void gdn_varlen_checks(const torch::Tensor& q, const torch::Tensor& k,
+                       const torch::Tensor& v, const torch::Tensor& beta,
+                       const torch::Tensor& decay_log) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(k.is_cuda() && k.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(v.is_cuda() && v.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(q.dim() == 4 && q.size(-1) == 64,
+              "gdn varlen kernels support (1, H, T, 64)");
+  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(),
+              "q, k, v / dout must share one (1, H, T, 64) shape");
+  TORCH_CHECK(beta.is_cuda() && decay_log.is_cuda());
+  TORCH_CHECK(beta.dim() == 3 && beta.size(0) == q.size(0) &&
+                  beta.size(1) == q.size(1) && beta.size(2) == q.size(2) &&
+                  decay_log.sizes() == beta.sizes(),
+              "beta and decay_log must be (1, H, T)");
+}
+
+}  // namespace
+
+torch::Tensor causal_conv_silu_fwd(torch::Tensor x, torch::Tensor w) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(w.size(1) <= 4, "conv kernel must be <= 4");
+  return conv_silu_fwd_impl<false>(x, w, nullptr, 0);
+}
+
+std::vector<torch::Tensor> causal_conv_silu_bwd(
+    torch::Tensor x, torch::Tensor w, torch::Tensor dy) {
+  return conv_silu_bwd_impl<false>(x, w, dy, nullptr, 0);
+}
+
+torch::Tensor causal_conv_silu_varlen_fwd(torch::Tensor x, torch::Tensor w,
+                                          torch::Tensor cu_seqlens) {
+  conv_varlen_checks(x, w);
+  auto docs = gdn_check_docs(cu_seqlens, x.size(0), x.size(1), x.device(),
+                             /*with_chunks=*/false);
+  return conv_silu_fwd_impl<true>(x, w, docs.cu_dev.data_ptr<int>(),
+                                  (int)docs.nseq);
+}
+
+std::vector<torch::Tensor> causal_conv_silu_varlen_bwd(
+    torch::Tensor x, torch::Tensor w, torch::Tensor dy,
+    torch::Tensor cu_seqlens) {
+  conv_varlen_checks(x, w);
+  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
+                  dy.sizes() == x.sizes(),
+              "dy must match x");
+  auto docs = gdn_check_docs(cu_seqlens, x.size(0), x.size(1), x.device(),
+                             /*with_chunks=*/false);
+  return conv_silu_bwd_impl<true>(x, w, dy, docs.cu_dev.data_ptr<int>(),
+                                  (int)docs.nseq);
 }
 
 std::vector<torch::Tensor> gdn_chunk_bwd_scan(
@@ -862,52 +1140,46 @@ std::vector<torch::Tensor> gdn_chunk_bwd_scan(
   auto f32 = torch::dtype(torch::kFloat32).device(q.device());
   auto drhs = torch::empty({B, H, S, 64}, f32);
   auto ds0 = torch::empty({B, H, nc, 64, 64}, f32);
-  auto stream = at::hip::getCurrentHIPStream();
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&d9d::gdn_chunk_bwd_scan_kernel<64>),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)sizeof(d9d::GdnBwdLds<64>));
-    hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&d9d::gdn_chunk_bwd_scan_kernel<32>),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)sizeof(d9d::GdnBwdLds<32>));
-    attr_set = true;
-  }
-  // same Dv-split heuristic as the forward kernel: duplicate the K-side
-  // work when B*H alone would leave half the CUs idle
-  if (B * H * 2 <= 384) {
-    hipLaunchKernelGGL(d9d::gdn_chunk_bwd_scan_kernel<32>,
-                       dim3((unsigned)(B * H), 2), dim3(256),
-                       sizeof(d9d::GdnBwdLds<32>), stream,
-                       reinterpret_cast<const __bf16*>(qc.data_ptr()),
-                       reinterpret_cast<const __bf16*>(kc.data_ptr()),
-                       reinterpret_cast<const __bf16*>(dc.data_ptr()),
-                       bc.data_ptr<float>(), gc.data_ptr<float>(),
-                       drhs.data_ptr<float>(), ds0.data_ptr<float>(),
-                       B * H, S);
-  } else {
-    hipLaunchKernelGGL(d9d::gdn_chunk_bwd_scan_kernel<64>,
-                       dim3((unsigned)(B * H), 1), dim3(256),
-                       sizeof(d9d::GdnBwdLds<64>), stream,
-                       reinterpret_cast<const __bf16*>(qc.data_ptr()),
-                       reinterpret_cast<const __bf16*>(kc.data_ptr()),
-                       reinterpret_cast<const __bf16*>(dc.data_ptr()),
-                       bc.data_ptr<float>(), gc.data_ptr<float>(),
-                       drhs.data_ptr<float>(), ds0.data_ptr<float>(),
-                       B * H, S);
-  }
+  gdn_bwd_scan_launch<false>(B * H, S, qc, kc, dc, bc, gc,
+                             drhs.data_ptr<float>(), ds0.data_ptr<float>(),
+                             nullptr, nullptr, 0, 0);
   return {drhs, ds0};
 }
 
-std::vector<torch::Tensor> gdn_chunk_fwd(
-    torch::Tensor q, torch::Tensor k, torch::Tensor v,
-    torch::Tensor beta, torch::Tensor decay_log, bool return_state,
-    bool return_aux, bool skip_out) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(q.size(-1) == 64 && v.size(-1) == 64,
-              "gdn_chunk_fwd supports Dk = Dv = 64");
+std::vector<torch::Tensor> gdn_chunk_bwd_scan_varlen(
+    torch::Tensor q, torch::Tensor k, torch::Tensor dout,
+    torch::Tensor beta, torch::Tensor decay_log, torch::Tensor cu_seqlens) {
+  gdn_varlen_checks(q, k, dout, beta, decay_log);
+  const int64_t H = q.size(1), T = q.size(2);
+  auto docs = gdn_check_docs(cu_seqlens, q.size(0), T, q.device(),
+                             /*with_chunks=*/true);
+  auto qc = q.contiguous();
+  auto kc = k.contiguous();
+  auto dc = dout.contiguous();
+  auto bc = beta.to(torch::kFloat32).contiguous();
+  auto gc = decay_log.to(torch::kFloat32).contiguous();
+  auto f32 = torch::dtype(torch::kFloat32).device(q.device());
+  auto drhs = torch::empty({1, H, T, 64}, f32);
+  auto ds0 = torch::empty({1, H, docs.nc, 64, 64}, f32);
+  gdn_bwd_scan_launch<true>(docs.nseq * H, T, qc, kc, dc, bc, gc,
+                            drhs.data_ptr<float>(), ds0.data_ptr<float>(),
+                            docs.cu_dev.data_ptr<int>(),
+                            docs.chunk_off_dev.data_ptr<int>(), (int)H,
+                            docs.nc);
+  return {drhs, ds0};
+}
+
+namespace {
+
+// Output allocation + launch shared by the dense and packed forward:
+// `n_state` workgroups (B*H, or nseq*H) each own one final state.
+template <bool VARLEN>
+std::vector<torch::Tensor> gdn_chunk_fwd_impl(
+    const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
+    const torch::Tensor& beta, const torch::Tensor& decay_log,
+    bool return_state, bool return_aux, bool skip_out,
+    std::vector<int64_t> state_lead, int64_t nc, const int* cu,
+    const int* chunk_off) {
   auto qc = q.contiguous();
   auto kc = k.contiguous();
   auto vc = v.contiguous();
@@ -917,11 +1189,11 @@ std::vector<torch::Tensor> gdn_chunk_fwd(
   auto out = skip_out ? torch::Tensor() : torch::empty_like(vc);
   __bf16* out_ptr =
       skip_out ? nullptr : reinterpret_cast<__bf16*>(out.data_ptr());
+  auto f32 = torch::dtype(torch::kFloat32).device(q.device());
   torch::Tensor fs;
   float* fs_ptr = nullptr;
   if (return_state) {
-    fs = torch::empty({B, H, 64, 64},
-                      torch::dtype(torch::kFloat32).device(q.device()));
+    fs = torch::empty({state_lead[0], state_lead[1], 64, 64}, f32);
     fs_ptr = fs.data_ptr<float>();
   }
   // aux outputs for the hand-derived backward: per-row solve results R and
@@ -929,48 +1201,15 @@ std::vector<torch::Tensor> gdn_chunk_fwd(
   torch::Tensor r_aux, s0_aux;
   float* r_ptr = nullptr;
   float* s0_ptr = nullptr;
-  const int64_t nc = (S + 63) / 64;
   if (return_aux) {
-    auto f32 = torch::dtype(torch::kFloat32).device(q.device());
     r_aux = torch::empty({B, H, S, 64}, f32);
     s0_aux = torch::empty({B, H, nc, 64, 64}, f32);
     r_ptr = r_aux.data_ptr<float>();
     s0_ptr = s0_aux.data_ptr<float>();
   }
-  auto stream = at::hip::getCurrentHIPStream();
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&d9d::gdn_chunk_fwd_kernel<64>),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)sizeof(d9d::GdnLds<64>));
-    hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&d9d::gdn_chunk_fwd_kernel<32>),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)sizeof(d9d::GdnLds<32>));
-    attr_set = true;
-  }
-  // Dv-split: below ~1.5 workgroups/CU the duplicated K-side work is
-  // cheaper than idle CUs.
-  if (B * H * 2 <= 384) {
-    hipLaunchKernelGGL(d9d::gdn_chunk_fwd_kernel<32>,
-                       dim3((unsigned)(B * H), 2), dim3(256),
-                       sizeof(d9d::GdnLds<32>), stream,
-                       reinterpret_cast<const __bf16*>(qc.data_ptr()),
-                       reinterpret_cast<const __bf16*>(kc.data_ptr()),
-                       reinterpret_cast<const __bf16*>(vc.data_ptr()),
-                       bc.data_ptr<float>(), gc.data_ptr<float>(),
-                       out_ptr, fs_ptr, r_ptr, s0_ptr, B * H, S);
-  } else {
-    hipLaunchKernelGGL(d9d::gdn_chunk_fwd_kernel<64>,
-                       dim3((unsigned)(B * H), 1), dim3(256),
-                       sizeof(d9d::GdnLds<64>), stream,
-                       reinterpret_cast<const __bf16*>(qc.data_ptr()),
-                       reinterpret_cast<const __bf16*>(kc.data_ptr()),
-                       reinterpret_cast<const __bf16*>(vc.data_ptr()),
-                       bc.data_ptr<float>(), gc.data_ptr<float>(),
-                       out_ptr, fs_ptr, r_ptr, s0_ptr, B * H, S);
-  }
+  gdn_fwd_launch<VARLEN>(state_lead[0] * state_lead[1], S, qc, kc, vc, bc, gc,
+                         out_ptr, fs_ptr, r_ptr, s0_ptr, cu, chunk_off, (int)H,
+                         nc);
   std::vector<torch::Tensor> outs;
   if (!skip_out) outs.push_back(out);
   if (return_state) outs.push_back(fs);
@@ -979,4 +1218,35 @@ std::vector<torch::Tensor> gdn_chunk_fwd(
     outs.push_back(s0_aux);
   }
   return outs;
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> gdn_chunk_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor beta, torch::Tensor decay_log, bool return_state,
+    bool return_aux, bool skip_out) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(q.size(-1) == 64 && v.size(-1) == 64,
+              "gdn_chunk_fwd supports Dk = Dv = 64");
+  return gdn_chunk_fwd_impl<false>(
+      q, k, v, beta, decay_log, return_state, return_aux, skip_out,
+      {q.size(0), q.size(1)}, (q.size(2) + 63) / 64, nullptr, nullptr);
+}
+
+// Packed documents: q, k, v (1, H, T, 64), one workgroup per (document,
+// head), zero state at each document start. Final state (nseq, H, 64, 64);
+// aux r (1, H, T, 64) by packed row, s0 (1, H, NC, 64, 64) by
+// chunk_off[doc] + local chunk.
+std::vector<torch::Tensor> gdn_chunk_fwd_varlen(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor beta, torch::Tensor decay_log, torch::Tensor cu_seqlens,
+    bool return_state, bool return_aux, bool skip_out) {
+  gdn_varlen_checks(q, k, v, beta, decay_log);
+  auto docs = gdn_check_docs(cu_seqlens, q.size(0), q.size(2), q.device(),
+                             /*with_chunks=*/true);
+  return gdn_chunk_fwd_impl<true>(
+      q, k, v, beta, decay_log, return_state, return_aux, skip_out,
+      {docs.nseq, q.size(1)}, docs.nc, docs.cu_dev.data_ptr<int>(),
+      docs.chunk_off_dev.data_ptr<int>());
 }

@@ -26,6 +26,39 @@ def _use_gdn_kernels(t: torch.Tensor) -> bool:
     return t.is_cuda and has_ext()
 
 
+def _check_cu_seqlens(cu_seqlens: torch.Tensor, batch: int, total: int) -> torch.Tensor:
+    """Validate packed-document boundaries for a (1, total, ...) input and
+    return them as a CPU int64 tensor. `cu_seqlens` is (nseq+1,) int32 on
+    either device: cu[0] = 0, cu[-1] = total, non-decreasing (zero-length
+    documents are legal)."""
+    if batch != 1:
+        raise ValueError(f"packed cu_seqlens input expects batch dim 1, got {batch}")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2:
+        raise ValueError("cu_seqlens must be an int32 tensor of shape (nseq+1,), nseq >= 1")
+    cu = cu_seqlens.detach().cpu().to(torch.int64)
+    if int(cu[0]) != 0 or int(cu[-1]) != total:
+        raise ValueError(
+            f"cu_seqlens must run from 0 to the {total} packed rows, "
+            f"got {int(cu[0])}..{int(cu[-1])}"
+        )
+    if bool((cu[1:] < cu[:-1]).any()):
+        raise ValueError("cu_seqlens must be non-decreasing")
+    return cu
+
+
+def _doc_chunk_layout(cu: torch.Tensor, chunk: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """Document-aligned chunk layout for packed rows: every document is
+    padded to a multiple of `chunk` so no chunk straddles a boundary.
+    `cu` is the CPU int64 boundaries. Returns (row, chunk_off): `row[t]` is
+    the padded-layout row of packed token t, `chunk_off[i]` the number of
+    chunks before document i (chunk_off[-1] = total chunks)."""
+    lens = cu[1:] - cu[:-1]
+    chunk_off = torch.zeros_like(cu)
+    chunk_off[1:] = ((lens + chunk - 1) // chunk).cumsum(0)
+    shift = torch.repeat_interleave(chunk_off[:-1] * chunk - cu[:-1], lens)
+    return torch.arange(int(cu[-1])) + shift, chunk_off
+
+
 class CausalShortDepthwiseConv1d(nn.Module):
     """Per-channel causal conv over the sequence (reference uses
     fla.modules.conv.causal_conv1d; this is the MI355X-native equivalent)."""
@@ -41,7 +74,15 @@ class CausalShortDepthwiseConv1d(nn.Module):
         with torch.no_grad():
             nn.init.normal_(self.weight, std=1.0 / math.sqrt(self.kernel_size))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:  # (B, S, C)
+    def forward(
+        self, x: torch.Tensor, cu_seqlens: torch.Tensor | None = None
+    ) -> torch.Tensor:  # (B, S, C)
+        """With `cu_seqlens` (packed documents, B == 1) a tap that would
+        reach before its document's first row contributes zero."""
+        if cu_seqlens is not None:
+            if _use_gdn_kernels(x) and x.dtype == torch.bfloat16:
+                return _CausalConvSiluVarlenFunction.apply(x, self.weight, cu_seqlens)
+            return self._eager_varlen(x, cu_seqlens)
         if _use_gdn_kernels(x) and x.dtype == torch.bfloat16:
             return _CausalConvSiluFunction.apply(x, self.weight)
         B, S, C = x.shape
@@ -49,6 +90,20 @@ class CausalShortDepthwiseConv1d(nn.Module):
         xt = F.pad(xt, (self.kernel_size - 1, 0))
         out = F.conv1d(xt, self.weight.unsqueeze(1), groups=C)
         return F.silu(out.transpose(1, 2))
+
+    def _eager_varlen(self, x: torch.Tensor, cu_seqlens: torch.Tensor) -> torch.Tensor:
+        """Eager packed-document conv: the tap d rows back is masked where
+        d exceeds the row's offset inside its document."""
+        B, S, C = x.shape
+        cu = _check_cu_seqlens(cu_seqlens, B, S)
+        K = self.kernel_size
+        offset = torch.arange(S) - torch.repeat_interleave(cu[:-1], cu[1:] - cu[:-1])
+        offset = offset.to(x.device).view(1, S, 1)
+        pre = x * self.weight[:, K - 1]
+        for d in range(1, K):
+            back = F.pad(x, (0, 0, d, 0))[:, :S]  # row s holds x[s - d]
+            pre = pre + back * (offset >= d).to(x.dtype) * self.weight[:, K - 1 - d]
+        return F.silu(pre)
 
 
 class _CausalConvSiluFunction(torch.autograd.Function):
@@ -66,6 +121,26 @@ class _CausalConvSiluFunction(torch.autograd.Function):
             x.contiguous(), w.contiguous(), dy.contiguous()
         )
         return dx, dw
+
+
+class _CausalConvSiluVarlenFunction(torch.autograd.Function):
+    """Packed-document fused conv + SiLU (csrc/gdn.hip); the extension
+    validates `cu_seqlens` on the host before it launches."""
+
+    @staticmethod
+    def forward(ctx, x, w, cu_seqlens):
+        ctx.save_for_backward(x, w, cu_seqlens)
+        return get_ext().causal_conv_silu_varlen_fwd(
+            x.contiguous(), w.contiguous(), cu_seqlens
+        )
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, cu_seqlens = ctx.saved_tensors
+        dx, dw = get_ext().causal_conv_silu_varlen_bwd(
+            x.contiguous(), w.contiguous(), dy.contiguous(), cu_seqlens
+        )
+        return dx, dw, None
 
 
 def step_gated_delta_rule(
@@ -104,12 +179,23 @@ def chunk_gated_delta_rule(
     beta: torch.Tensor,  # (B, H, S) write strength in [0, 1]
     decay_log: torch.Tensor,  # (B, H, S) log decay (<= 0)
     chunk_size: int = 64,
+    cu_seqlens: torch.Tensor | None = None,  # packed documents (B == 1)
 ) -> torch.Tensor:
     """GPU (Dk = Dv = 64): fused CDNA4 chunk kernel (csrc/gdn.hip) — the
     fp32 state stays LDS-resident across the chunk loop and every chunk
     GEMM lands on MFMA; backward recomputes through the torch WY graph
     (a native bwd kernel is the follow-up). Other shapes / CPU: the
-    chunked-parallel WY torch path below."""
+    chunked-parallel WY torch path below.
+
+    `cu_seqlens` ((nseq+1,) int32, either device) marks packed documents
+    along S: the state is zero at each document start and no gradient
+    crosses a boundary, so rows cu[i]:cu[i+1] equal a call on document i
+    alone. The kernel path runs one workgroup per (document, head)."""
+    if cu_seqlens is not None:
+        # one host copy serves this check, the backward's chunk layout and
+        # the kernels' host-side validation / grid sizing
+        cu_seqlens = cu_seqlens.detach().cpu()
+        _check_cu_seqlens(cu_seqlens, q.shape[0], q.shape[2])
     use_kernel = (
         _use_gdn_kernels(q)
         and q.shape[-1] == 64
@@ -119,23 +205,30 @@ def chunk_gated_delta_rule(
     if torch.is_grad_enabled() and any(
         t.requires_grad for t in (q, k, v, beta, decay_log)
     ):
-        return _GdnChunkFunction.apply(q, k, v, beta, decay_log, chunk_size, use_kernel)
+        return _GdnChunkFunction.apply(
+            q, k, v, beta, decay_log, chunk_size, use_kernel, cu_seqlens
+        )
     if use_kernel:
-        return _gdn_kernel_fwd(q, k, v, beta, decay_log)
-    return _chunk_gated_delta_rule_torch(q, k, v, beta, decay_log, chunk_size)
+        return _gdn_kernel_fwd(q, k, v, beta, decay_log, cu_seqlens)
+    return _chunk_gated_delta_rule_torch(
+        q, k, v, beta, decay_log, chunk_size, cu_seqlens
+    )
 
 
-def _gdn_kernel_fwd(q, k, v, beta, decay_log):
-    out = get_ext().gdn_chunk_fwd(
+def _gdn_kernel_fwd(q, k, v, beta, decay_log, cu_seqlens=None):
+    args = (
         q.to(torch.bfloat16).contiguous(),
         k.to(torch.bfloat16).contiguous(),
         v.to(torch.bfloat16).contiguous(),
         beta.contiguous(),
         decay_log.contiguous(),
-        False,
-        False,
-        False,
-    )[0]
+    )
+    if cu_seqlens is None:
+        out = get_ext().gdn_chunk_fwd(*args, False, False, False)[0]
+    else:
+        out = get_ext().gdn_chunk_fwd_varlen(
+            *args, cu_seqlens, False, False, False
+        )[0]
     return out.to(v.dtype)
 
 
@@ -147,25 +240,27 @@ class _GdnChunkFunction(torch.autograd.Function):
     autograd graph)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, beta, decay_log, chunk_size, use_kernel):
+    def forward(ctx, q, k, v, beta, decay_log, chunk_size, use_kernel,
+                cu_seqlens=None):
         if use_kernel:
-            out = _gdn_kernel_fwd(q, k, v, beta, decay_log)
+            out = _gdn_kernel_fwd(q, k, v, beta, decay_log, cu_seqlens)
         else:
             with torch.no_grad():
                 out = _chunk_gated_delta_rule_torch(
-                    q, k, v, beta, decay_log, chunk_size
+                    q, k, v, beta, decay_log, chunk_size, cu_seqlens
                 )
         ctx.save_for_backward(q, k, v, beta, decay_log)
         ctx.chunk_size = chunk_size
+        ctx.cu_seqlens = cu_seqlens
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, beta, decay_log = ctx.saved_tensors
         dq, dk, dv, dbeta, dg = _chunk_gdn_backward(
-            q, k, v, beta, decay_log, dout, ctx.chunk_size
+            q, k, v, beta, decay_log, dout, ctx.chunk_size, ctx.cu_seqlens
         )
-        return dq, dk, dv, dbeta, dg, None, None
+        return dq, dk, dv, dbeta, dg, None, None, None
 
 
 def _chunk_gated_delta_rule_torch(
@@ -175,6 +270,7 @@ def _chunk_gated_delta_rule_torch(
     beta: torch.Tensor,
     decay_log: torch.Tensor,
     chunk_size: int = 64,
+    cu_seqlens: torch.Tensor | None = None,
 ) -> torch.Tensor:
     """Chunked-parallel gated delta rule (WY form, replacing fla-core's
     `chunk_gated_delta_rule` CUDA path with MFMA matmuls via rocBLAS).
@@ -190,7 +286,22 @@ def _chunk_gated_delta_rule_torch(
 
     All decay ratios have t >= j so exp(gc_t - gc_j) <= 1: numerically safe.
     One unit-lower triangular solve + ~4 matmuls per chunk; chunks run
-    sequentially over S. Matches step_gated_delta_rule to fp32 tolerance."""
+    sequentially over S. Matches step_gated_delta_rule to fp32 tolerance.
+
+    With `cu_seqlens` (packed documents, B == 1) each document is run on
+    its own from a zero state — a per-document loop; this is the CPU
+    fallback and the numerics reference, not a hot path."""
+    if cu_seqlens is not None:
+        cu = _check_cu_seqlens(cu_seqlens, q.shape[0], q.shape[2]).tolist()
+        outs = [
+            _chunk_gated_delta_rule_torch(
+                q[:, :, s:e], k[:, :, s:e], v[:, :, s:e],
+                beta[:, :, s:e], decay_log[:, :, s:e], chunk_size,
+            )
+            for s, e in zip(cu[:-1], cu[1:])
+            if e > s
+        ]
+        return torch.cat(outs, dim=2) if outs else torch.zeros_like(v)
     B, H, S, Dk = q.shape
     Dv = v.shape[-1]
     C = min(chunk_size, S)
@@ -236,7 +347,8 @@ def _chunk_gated_delta_rule_torch(
     return torch.cat(outs, dim=2).to(v.dtype)
 
 
-def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64):
+def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
+                        cu_seqlens=None):
     """Explicit backward of `_chunk_gated_delta_rule_torch` (same WY chunk
     formulation), derived by hand so the backward does NOT rebuild and
     backprop the sequential autograd graph. Only the inter-chunk dState
@@ -255,18 +367,51 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64):
         drhs = A^{-T} dR;          dT = -(b_row * drhs)
         dS0  = Eend dS1 + (E*K)^T dT + (E*Q)^T dO
     and all remaining leaf grads are local chunk expressions of
-    (dO, dS1, dR, drhs) — see the body. Returns (dq, dk, dv, dbeta, dg)."""
+    (dO, dS1, dR, drhs) — see the body. Returns (dq, dk, dv, dbeta, dg).
+
+    Packed documents (`cu_seqlens`, B == 1): the rows are first gathered
+    into a document-aligned layout, each document padded to a chunk
+    multiple with the same harmless zero rows as the tail pad below, so no
+    chunk straddles a boundary. The scans then start from zero at every
+    document's first (forward) / last (reverse) chunk, the batched leaf
+    code runs unchanged over all chunks, and the results are scattered
+    back to packed rows — no per-document launches."""
     B, H, S, Dk = q.shape
     Dv = v.shape[-1]
-    C = min(chunk_size, S)
     dtype_v = v.dtype
     q32, k32, v32 = q.float(), k.float(), v.float()
     b32, g32 = beta.float(), decay_log.float()
     do32 = dout.float()
 
+    varlen = cu_seqlens is not None
+    if varlen:
+        cu = _check_cu_seqlens(cu_seqlens, B, S)
+        if S == 0:
+            return tuple(torch.zeros_like(t) for t in (q, k, v, beta, decay_log))
+        C = chunk_size
+        row, chunk_off = _doc_chunk_layout(cu, C)
+        row = row.to(q.device)
+        nonempty = cu[1:] > cu[:-1]
+        doc_first = chunk_off[:-1][nonempty]      # first chunk of each document
+        doc_last = chunk_off[1:][nonempty] - 1    # last chunk of each document
+        Sp_doc = int(chunk_off[-1]) * C
+
+        def to_doc_layout(t):
+            z = t.new_zeros(B, H, Sp_doc, *t.shape[3:])
+            return z.index_copy_(2, row, t)
+
+        q32, k32, v32, do32, b32, g32 = (
+            to_doc_layout(t) for t in (q32, k32, v32, do32, b32, g32)
+        )
+        S_lay = Sp_doc
+    else:
+        C = min(chunk_size, S)
+        doc_first = doc_last = None
+        S_lay = S
+
     # pad S to a chunk multiple (padded tail: beta = 0, g = 0, q/k/v/do = 0
     # => the padded rows write nothing into the state and produce no grads)
-    pad = (C - S % C) % C
+    pad = (C - S_lay % C) % C
     if pad:
         zq = q32.new_zeros(B, H, pad, Dk)
         q32 = torch.cat([q32, zq], 2)
@@ -275,8 +420,12 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64):
         do32 = torch.cat([do32, do32.new_zeros(B, H, pad, Dv)], 2)
         b32 = torch.cat([b32, b32.new_zeros(B, H, pad)], 2)
         g32 = torch.cat([g32, g32.new_zeros(B, H, pad)], 2)
-    Sp = S + pad
+    Sp = S_lay + pad
     nc = Sp // C
+    # chunks at which the torch scans restart from zero (dense: only the
+    # scans' own initial zero state)
+    first_set = set() if doc_first is None else set(doc_first.tolist())
+    last_set = set() if doc_last is None else set(doc_last.tolist())
 
     # (B, H, nc, C, D) chunked views
     Qc = q32.view(B, H, nc, C, Dk)
@@ -311,15 +460,27 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64):
         ext = get_ext()
         q16 = q32.to(torch.bfloat16).contiguous()
         k16 = k32.to(torch.bfloat16).contiguous()
-        r_flat, S0s = ext.gdn_chunk_fwd(
-            q16, k16, v32.to(torch.bfloat16).contiguous(),
-            b32.contiguous(), g32.contiguous(), False, True, True,
-        )
+        v16 = v32.to(torch.bfloat16).contiguous()
+        do16 = do32.to(torch.bfloat16).contiguous()
+        if varlen:
+            # boundaries of the document-aligned layout: whole chunks only
+            cu_lay = (chunk_off * C).to(torch.int32)
+            r_flat, S0s = ext.gdn_chunk_fwd_varlen(
+                q16, k16, v16, b32.contiguous(), g32.contiguous(), cu_lay,
+                False, True, True,
+            )
+            drhs_flat, dS0s = ext.gdn_chunk_bwd_scan_varlen(
+                q16, k16, do16, b32.contiguous(), g32.contiguous(), cu_lay,
+            )
+        else:
+            r_flat, S0s = ext.gdn_chunk_fwd(
+                q16, k16, v16, b32.contiguous(), g32.contiguous(),
+                False, True, True,
+            )
+            drhs_flat, dS0s = ext.gdn_chunk_bwd_scan(
+                q16, k16, do16, b32.contiguous(), g32.contiguous(),
+            )
         Rs = r_flat.view(B, H, nc, C, Dv)
-        drhs_flat, dS0s = ext.gdn_chunk_bwd_scan(
-            q16, k16, do32.to(torch.bfloat16).contiguous(),
-            b32.contiguous(), g32.contiguous(),
-        )
         drhss = drhs_flat.view(B, H, nc, C, Dv)
     else:
         M = (bc.unsqueeze(-1) * kk * ratio).tril(-1)
@@ -330,6 +491,8 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64):
         Rs = torch.empty(B, H, nc, C, Dv, dtype=torch.float32, device=q.device)
         state = torch.zeros(B, H, Dk, Dv, dtype=torch.float32, device=q.device)
         for i in range(nc):
+            if i in first_set:
+                state = torch.zeros_like(state)
             S0s[:, :, i] = state
             rhs = bc[:, :, i].unsqueeze(-1) * (
                 Vc[:, :, i] - torch.matmul(EK[:, :, i], state)
@@ -347,6 +510,8 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64):
         AT = A.transpose(-1, -2)
         dS = torch.zeros(B, H, Dk, Dv, dtype=torch.float32, device=q.device)
         for i in range(nc - 1, -1, -1):
+            if i in last_set:
+                dS = torch.zeros_like(dS)
             dR = torch.matmul(wK[:, :, i], dS) + torch.matmul(
                 N[:, :, i].transpose(-1, -2), dOc[:, :, i]
             )
@@ -366,6 +531,9 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64):
     dS1s = torch.cat(
         [dS0s[:, :, 1:], torch.zeros_like(dS0s[:, :, :1])], dim=2
     )  # per-chunk dL/d(S1)
+    if varlen:
+        # a document's last chunk hands its state to nobody
+        dS1s[:, :, doc_last.to(q.device)] = 0.0
 
     # ---- batched leaf gradients --------------------------------------------
     dgc = torch.zeros_like(gc)
@@ -419,11 +587,11 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64):
     # gc = cumsum(g): dg_t = sum_{tau >= t} dgc_tau  (within the chunk)
     dg = dgc.flip(-1).cumsum(-1).flip(-1)
 
-    dq = dQ.reshape(B, H, Sp, Dk)[:, :, :S]
-    dk = dK.reshape(B, H, Sp, Dk)[:, :, :S]
-    dv = dV.reshape(B, H, Sp, Dv)[:, :, :S]
-    dbeta = db.reshape(B, H, Sp)[:, :, :S]
-    dg = dg.reshape(B, H, Sp)[:, :, :S]
+    def to_rows(t):  # (B, H, nc, C, ...) -> the caller's (B, H, S, ...) rows
+        t = t.reshape(B, H, Sp, *t.shape[4:])
+        return t.index_select(2, row) if varlen else t[:, :, :S]
+
+    dq, dk, dv, dbeta, dg = (to_rows(t) for t in (dQ, dK, dV, db, dg))
     return (
         dq.to(q.dtype), dk.to(k.dtype), dv.to(dtype_v),
         dbeta.to(beta.dtype), dg.to(decay_log.dtype),
@@ -492,13 +660,28 @@ class GatedDeltaNet(nn.Module):
         for m in (self.q_conv, self.k_conv, self.v_conv, self.decay_gate, self.out_norm):
             m.reset_parameters()
 
-    def forward(self, hidden_states: torch.Tensor, rotary_cos_sin=None) -> torch.Tensor:
+    def forward(
+        self,
+        hidden_states: torch.Tensor,
+        rotary_cos_sin=None,
+        cu_seqlens: torch.Tensor | None = None,  # packed documents (B == 1)
+    ) -> torch.Tensor:
+        """With `cu_seqlens` ((nseq+1,) int32, as GroupedQueryAttention
+        takes it) rows cu[i]:cu[i+1] are document i: neither the short
+        convs nor the recurrent state see across a boundary."""
         B, S, _ = hidden_states.shape
         H, Hkv = self.num_heads, self.num_kv_heads
+        if cu_seqlens is not None:
+            assert B == 1, "packed cu_seqlens input expects batch dim 1"
+            # one host copy for the three convs and the recurrence
+            cu_seqlens = cu_seqlens.detach().cpu()
 
-        q = self.q_conv(self.q_proj(hidden_states)).view(B, S, Hkv, self.head_k_dim)
-        k = self.k_conv(self.k_proj(hidden_states)).view(B, S, Hkv, self.head_k_dim)
-        v = self.v_conv(self.v_proj(hidden_states)).view(B, S, H, self.head_v_dim)
+        q = self.q_conv(self.q_proj(hidden_states), cu_seqlens).view(
+            B, S, Hkv, self.head_k_dim)
+        k = self.k_conv(self.k_proj(hidden_states), cu_seqlens).view(
+            B, S, Hkv, self.head_k_dim)
+        v = self.v_conv(self.v_proj(hidden_states), cu_seqlens).view(
+            B, S, H, self.head_v_dim)
 
         if H != Hkv:  # GQA expansion
             rep = H // Hkv
@@ -518,6 +701,7 @@ class GatedDeltaNet(nn.Module):
             v.permute(0, 2, 1, 3).to(v.dtype),
             beta.permute(0, 2, 1),
             decay.permute(0, 2, 1),
+            cu_seqlens=cu_seqlens,
         ).permute(0, 2, 1, 3)  # (B,S,H,Dv)
 
         out = self.out_norm(out)
