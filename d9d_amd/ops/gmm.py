@@ -3,9 +3,10 @@
 out[rows_e] = a[rows_e] @ b[e]  for each expert e, rows partitioned by
 `batch_sizes` (CPU int64, per-expert row counts, in order).
 
-GPU: hand-written CDNA4 MFMA grouped-GEMM kernel (csrc/gmm.hip) with
-tile-list scheduling over ragged group sizes. Until the kernel lands the
-GPU path falls back to per-expert rocBLAS GEMMs (library GEMM).
+GPU: hand-written CDNA4 MFMA grouped-GEMM kernels (csrc/gmm.hip), one
+launch over all experts with tile-list scheduling over ragged group sizes.
+The per-expert torch loops below serve CPU tensors and are the reference
+the GPU tests compare against.
 Backward is direction-gated via GLOBAL_GRAD_CONTEXT (da = g @ b^T grouped;
 db[e] = a[rows_e]^T @ g[rows_e]).
 """

@@ -7,13 +7,38 @@ from d9d_amd.ops.gmm import gmm, _gmm_loop, _gmm_accum_db
 
 
 def _rand_sizes(E, total, device="cpu"):
-    """Ragged per-expert row counts summing to `total`, incl. zeros."""
+    """Ragged per-expert row counts summing to `total`, incl. zeros.
+
+    A list `total` is taken as the explicit per-expert sizes."""
+    if isinstance(total, (list, tuple)):
+        assert len(total) == E
+        return torch.tensor(total, dtype=torch.int64)
     g = torch.Generator().manual_seed(0)
     w = torch.rand(E, generator=g)
     w[::7] = 0  # some empty experts
     sizes = (w / w.sum() * total).long()
     sizes[0] += total - sizes.sum()
     return sizes
+
+
+def _explicit(sizes, K, N):
+    """One case with explicit per-expert sizes (id: rows joined by '_')."""
+    name = "_".join(map(str, sizes))
+    return pytest.param(len(sizes), list(sizes), K, N, id=f"rows{name}-{K}-{N}")
+
+
+# Shapes that reach the corners of the 8-phase forward/dgrad pipeline. Rows:
+# one empty expert, one expert spanning two m-tiles with a 1-row second tile,
+# two partial tiles.
+_EDGE_ROWS = [0, 257, 5, 64]
+_EDGE_8PHASE = [
+    _explicit(_EDGE_ROWS, 64, 192),    # one k-tile: no B(1) prologue, vmcnt(0) boundary
+    _explicit(_EDGE_ROWS, 128, 256),   # two k-tiles, 256-wide n-tile
+    _explicit(_EDGE_ROWS, 96, 256),    # one full k-tile + the K % 64 == 32 tail
+    _explicit(_EDGE_ROWS, 160, 80),    # three k-tiles + tail, one ragged 192-tile
+    _explicit(_EDGE_ROWS, 160, 272),   # two 192-wide n-tiles, the second ragged
+    _explicit([300], 96, 192),         # E == 1: cached offsets
+]
 
 
 @pytest.mark.gpu
@@ -24,11 +49,13 @@ def _rand_sizes(E, total, device="cpu"):
         (128, 32768, 768, 576),
         (16, 1000, 576, 768),   # ragged, non-multiple
         (4, 130, 100, 72),      # tiny + edge tiles
+        *_EDGE_8PHASE,
     ],
 )
 def test_gmm_forward_parity(E, total, K, N):
     device = torch.device("cuda")
     sizes = _rand_sizes(E, total)
+    total = int(sizes.sum())
     a = torch.randn(total, K, dtype=torch.bfloat16, device=device)
     b = torch.randn(E, K, N, dtype=torch.bfloat16, device=device) * 0.1
 
@@ -45,10 +72,15 @@ def test_gmm_forward_parity(E, total, K, N):
     (8, 4096, 576, 768),    # BK 192, BN 256 (the bench's down-projection wgrad)
     (4, 2048, 1152, 576),   # BK 192, BN 192
     (16, 999, 100, 72),     # legacy fallback (K % 8 != 0)
+    # row-tile counts 0/1/1/1/2/3: empty-expert zero fill, zero-source row
+    # tails, and the 16-byte column clamp at the edge of both dims
+    _explicit([0, 1, 63, 64, 65, 129], 72, 200),
+    _explicit([0, 1, 63, 64, 65, 129], 192, 256),
 ])
 def test_gmm_db_parity(E, total, K, N):
     device = torch.device("cuda")
     sizes = _rand_sizes(E, total)
+    total = int(sizes.sum())
     a = torch.randn(total, K, dtype=torch.bfloat16, device=device)
     g = torch.randn(total, N, dtype=torch.bfloat16, device=device) * 0.1
 
@@ -89,11 +121,13 @@ def test_gmm_autograd_path_uses_kernel():
         (128, 32768, 576, 768),
         (16, 1000, 576, 768),   # ragged, non-multiple
         (4, 130, 100, 72),      # tiny + edge tiles
+        *_EDGE_8PHASE,
     ],
 )
 def test_gmm_nt_forward_parity(E, total, K, N):
     device = torch.device("cuda")
     sizes = _rand_sizes(E, total)
+    total = int(sizes.sum())
     a = torch.randn(total, K, dtype=torch.bfloat16, device=device)
     w = torch.randn(E, N, K, dtype=torch.bfloat16, device=device) * 0.1
     from d9d_amd.ops import _ext
