@@ -33,10 +33,12 @@ D9D_DEVICE f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
 
 // XOR swizzles keep ds_read_b128 bank-conflict-free (guide G4). The XOR must
 // stay inside the LDS row: row-major [64][D] tiles (D*2-byte rows) use mask
-// kSwzRM(D); transposed [D][64] tiles (128-byte rows) use mask 7.
+// kSwzRM(D); transposed [D][64] tiles (128-byte rows) use mask 7. A mask of
+// m bits needs the row size to be a multiple of 16 << m bytes: D = 96 has
+// 192-byte rows (a multiple of 64 only), so it takes the 2-bit mask.
 template <int D>
 constexpr int swz_rm_mask() {
-  return D == 128 ? 15 : (D >= 64 ? 7 : 3);
+  return D == 128 ? 15 : (D == 64 ? 7 : 3);
 }
 
 union ushort2_t {  // 4 bf16 lanes packed for one 8-byte LDS store
@@ -1452,7 +1454,8 @@ std::vector<torch::Tensor> flash_attn_bwd(
     torch::Tensor out, torch::Tensor lse,
     c10::optional<torch::Tensor> cu_seqlens_q,
     c10::optional<torch::Tensor> cu_seqlens_k,
-    bool causal, double softmax_scale, int64_t window_left, int64_t q_offset) {
+    bool causal, double softmax_scale, int64_t window_left, int64_t q_offset,
+    c10::optional<torch::Tensor> dlse) {
   const bool varlen = cu_seqlens_q.has_value();
   if (varlen) {
     dout = dout.unsqueeze(0);
@@ -1510,6 +1513,15 @@ std::vector<torch::Tensor> flash_attn_bwd(
                        reinterpret_cast<const __bf16*>(dop.data_ptr()),
                        reinterpret_cast<const __bf16*>(op.data_ptr()),
                        delta.data_ptr<float>(), B, Sq, Hq, D_pad);
+  }
+  if (dlse.has_value()) {
+    // lse is itself an output: d(lse_i)/d(S_ij) = P_ij, so its upstream grad
+    // enters as dS = P*(dP - delta) + P*dlse = P*(dP - (delta - dlse)).
+    auto g = dlse->to(torch::kFloat32);
+    if (varlen) g = g.unsqueeze(0);
+    TORCH_CHECK(g.is_cuda() && g.sizes() == delta.sizes(),
+                "flash_attn_bwd: dlse must have the layout of lse");
+    delta.sub_(g);
   }
 
   // v2 geometry experiment (kv-64 tiles, 3 workgroups/CU): opt-in via

@@ -30,7 +30,7 @@ std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q, t
                                           c10::optional<torch::Tensor> cu_seqlens_q,
                                           c10::optional<torch::Tensor> cu_seqlens_k,
                                           bool causal, double softmax_scale, int64_t window_left,
-                                          int64_t q_offset);
+                                          int64_t q_offset, c10::optional<torch::Tensor> dlse);
 torch::Tensor mfma_selfcheck(torch::Tensor a, torch::Tensor b);
 
 // moe_router.hip
@@ -120,7 +120,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gmm_nt", &gmm_nt, "CDNA4 grouped GEMM, weight (E,N,K)");
   m.def("gmm_db", &gmm_db, "CDNA4 grouped GEMM weight-grad");
   m.def("rope_qk", &rope_qk, "fused q/k rotary embedding");
-  m.def("cce_fwd", &cce_fwd, "fused linear cross-entropy forward (lse + target logit)");
+  m.def("cce_fwd", &cce_fwd, "fused linear cross-entropy forward (lse, target logit, lse of the bf16-rounded logits)");
   m.def("moe_gather_rows", &moe_gather_rows, "MoE row gather (optional scale)");
   m.def("moe_csr_combine", &moe_csr_combine, "MoE weighted replica combine");
   m.def("moe_row_dot", &moe_row_dot, "per-row dot for prob grads");

@@ -43,11 +43,18 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
     const int64_t* __restrict__ targets,  // (T,)
     float* __restrict__ lse_out,          // (T,)
     float* __restrict__ tgt_out,          // (T,) target logit or -inf
+    float* __restrict__ lse_bf_out,       // (T,) lse of the bf16-ROUNDED logits
     int T, int V, int K) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* e_lds = reinterpret_cast<bf16_t*>(smem);       // [64][K] swizzled
   bf16_t* c_lds = e_lds + 64 * K;                        // [128][KT] swizzled
-  constexpr int kSwz = (KT == 64) ? 7 : 15;  // XOR stays within the KT*2 row
+  // XOR swizzles must stay inside their LDS row. The classifier tile has
+  // KT*2-byte rows. The e rows are K*2 bytes: a multiple of 256 when
+  // K % 128 == 0 (always the case at KT == 128), but only of 128 otherwise,
+  // where a 4-bit XOR would spill into the next row (and, from row 63, into
+  // the classifier tile). So e_lds and c_lds both swizzle with kSwz: 3 bits
+  // at KT == 64, 4 bits at KT == 128.
+  constexpr int kSwz = (KT == 64) ? 7 : 15;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;   // 8 waves: (vocab half) x (4 m-tiles)
@@ -86,14 +93,14 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
     }
   };
 
-  // ---- stage e block (row-major [64][K], ((row&15)<<4) swizzle) and the
+  // ---- stage e block (row-major [64][K], ((row&kSwz)<<4) swizzle) and the
   // first classifier tile; ONE barrier covers both ---------------------------
   for (int idx = threadIdx.x * 8; idx < 64 * K; idx += 512 * 8) {
     const int row = idx / K;
     const int col = idx % K;
     const int g_row = min(t0 + row, T - 1);
     const bf16x8 val = *reinterpret_cast<const bf16x8*>(e + (int64_t)g_row * K + col);
-    const int byte = (col * 2) ^ ((row & 15) << 4);
+    const int byte = (col * 2) ^ ((row & kSwz) << 4);
     *reinterpret_cast<bf16x8*>(
         reinterpret_cast<char*>(e_lds) + row * (K * 2) + byte) = val;
   }
@@ -103,12 +110,21 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
 
   const int my_row_local = m_tile * 16 + (lane & 15);
 
-  float m_run[4], l_run[4], tgt[4];
+  // lb_run: what the online sum gains when every logit z is rounded to bf16
+  // (zb), to first order: sum exp(z - m) * (zb - z); exp(zb - z) - 1 - (zb - z)
+  // is below (2^-9 z)^2 / 2: 5e-4 at |z| < 16 and 2e-3 at |z| < 32 (under the
+  // 4e-3 bf16 step of the dlogits), 8e-3 at |z| < 64. The form assumes
+  // |z| < 64; at |z| >= 128 the rounding step is 0.5 and it no longer holds. The backward recomputes the logits as a bf16
+  // GEMM output, and exp(bf16 logit - lse) only sums to 1 over a row against
+  // the lse of the ROUNDED logits: against the fp32 one every p is off by the
+  // rounding of its own logit (up to 3% at |logit| in [8, 16)).
+  float m_run[4], l_run[4], lb_run[4], tgt[4];
   int tg_row[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     m_run[r] = -1e30f;
     l_run[r] = 0.f;
+    lb_run[r] = 0.f;
     tgt[r] = -1e30f;
     tg_row[r] = (int)targets[min(t0 + m_tile * 16 + (lane >> 4) * 4 + r, T - 1)];
   }
@@ -126,7 +142,7 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
 #pragma unroll
     for (int ks = 0; ks < KT / 32; ++ks) {
       const int kk = kt * KT + ks * 32 + (lane >> 4) * 8;
-      const int ebyte = (kk * 2) ^ ((my_row_local & 15) << 4);
+      const int ebyte = (kk * 2) ^ ((my_row_local & kSwz) << 4);
       const bf16x8 ea = *reinterpret_cast<const bf16x8*>(
           reinterpret_cast<char*>(e_lds) + my_row_local * (K * 2) + ebyte);
 #pragma unroll
@@ -165,14 +181,20 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
         const float mx = fmaxf(fmaxf(vals[0][r], vals[1][r]),
                                fmaxf(vals[2][r], vals[3][r]));
         const float m_new = fmaxf(m_run[r], mx);
-        float add = 0.f;
+        float add = 0.f, add_bf = 0.f;
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-          add += __builtin_amdgcn_exp2f((vals[nt][r] - m_new) * kLog2eC);
+          const float ex =
+              __builtin_amdgcn_exp2f((vals[nt][r] - m_new) * kLog2eC);
+          add += ex;
+          // native RNE convert on gfx950
+          const float vb = static_cast<float>(static_cast<bf16_t>(vals[nt][r]));
+          add_bf = fmaf(ex, vb - vals[nt][r], add_bf);
         }
-        l_run[r] = l_run[r] *
-                       __builtin_amdgcn_exp2f((m_run[r] - m_new) * kLog2eC) +
-                   add;
+        const float rescale =
+            __builtin_amdgcn_exp2f((m_run[r] - m_new) * kLog2eC);
+        l_run[r] = l_run[r] * rescale + add;
+        lb_run[r] = lb_run[r] * rescale + add_bf;
         m_run[r] = m_new;
       }
 #pragma unroll
@@ -194,16 +216,20 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
     for (int off = 1; off < 16; off <<= 1) {
       const float mo = __shfl_xor(m_run[r], off, 64);
       const float lo = __shfl_xor(l_run[r], off, 64);
+      const float lbo = __shfl_xor(lb_run[r], off, 64);
       const float m2 = fmaxf(m_run[r], mo);
-      l_run[r] = l_run[r] * __builtin_amdgcn_exp2f((m_run[r] - m2) * kLog2eC) +
-                 lo * __builtin_amdgcn_exp2f((mo - m2) * kLog2eC);
+      const float sa = __builtin_amdgcn_exp2f((m_run[r] - m2) * kLog2eC);
+      const float sb = __builtin_amdgcn_exp2f((mo - m2) * kLog2eC);
+      l_run[r] = l_run[r] * sa + lo * sb;
+      lb_run[r] = lb_run[r] * sa + lbo * sb;
       m_run[r] = m2;
       tgt[r] = fmaxf(tgt[r], __shfl_xor(tgt[r], off, 64));
     }
   }
-  // scratch (reuses c_lds): per half, per row: lse and tgt.
+  // scratch (reuses c_lds): per half, per row: lse, tgt and rounded lse.
   float* half_lse = reinterpret_cast<float*>(c_lds);          // [2][64]
   float* half_tgt = half_lse + 2 * 64;                        // [2][64]
+  float* half_lbf = half_tgt + 2 * 64;                        // [2][64]
   __syncthreads();
   if ((lane & 15) == 0) {
 #pragma unroll
@@ -211,6 +237,8 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
       const int row_l = m_tile * 16 + (lane >> 4) * 4 + r;
       half_lse[vhalf * 64 + row_l] = m_run[r] + __logf(fmaxf(l_run[r], 1e-30f));
       half_tgt[vhalf * 64 + row_l] = tgt[r];
+      half_lbf[vhalf * 64 + row_l] =
+          m_run[r] + __logf(fmaxf(l_run[r] + lb_run[r], 1e-30f));
     }
   }
   __syncthreads();
@@ -227,6 +255,12 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
             __builtin_amdgcn_exp2f((a - mx) * kLog2eC) +
             __builtin_amdgcn_exp2f((b - mx) * kLog2eC));
         tgt_out[row_g] = fmaxf(half_tgt[row_l], half_tgt[64 + row_l]);
+        const float ab = half_lbf[row_l];
+        const float bb = half_lbf[64 + row_l];
+        const float mb = fmaxf(ab, bb);
+        lse_bf_out[row_g] = mb + __logf(
+            __builtin_amdgcn_exp2f((ab - mb) * kLog2eC) +
+            __builtin_amdgcn_exp2f((bb - mb) * kLog2eC));
       }
     }
   }
@@ -249,7 +283,8 @@ std::vector<torch::Tensor> cce_fwd(
 
   auto lse = torch::empty({T}, e.options().dtype(torch::kFloat32));
   auto tgt = torch::empty({T}, e.options().dtype(torch::kFloat32));
-  if (T == 0) return {lse, tgt};
+  auto lse_bf = torch::empty({T}, e.options().dtype(torch::kFloat32));
+  if (T == 0) return {lse, tgt, lse_bf};
   auto stream = at::hip::getCurrentHIPStream();
   auto tgts = targets.contiguous();
 #define LAUNCH_CCE(KT)                                                        \
@@ -258,10 +293,10 @@ std::vector<torch::Tensor> cce_fwd(
                      reinterpret_cast<const __bf16*>(e.data_ptr()),           \
                      reinterpret_cast<const __bf16*>(c.data_ptr()),           \
                      tgts.data_ptr<int64_t>(), lse.data_ptr<float>(),         \
-                     tgt.data_ptr<float>(), T, V, K)
+                     tgt.data_ptr<float>(), lse_bf.data_ptr<float>(), T, V, K)
   if (wide) LAUNCH_CCE(128); else LAUNCH_CCE(64);
 #undef LAUNCH_CCE
-  return {lse, tgt};
+  return {lse, tgt, lse_bf};
 }
 
 namespace d9d {

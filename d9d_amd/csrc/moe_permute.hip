@@ -111,11 +111,27 @@ __global__ void row_dot_kernel(
 
 }  // namespace d9d
 
+// Every pointer argument is reinterpreted by the kernels: a wrong device,
+// dtype or stride would read garbage (or out of bounds) without these.
+static void check_moe_arg(const torch::Tensor& t, torch::ScalarType dtype,
+                          int64_t dim, const char* op, const char* name) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on the GPU");
+  TORCH_CHECK(t.scalar_type() == dtype, op, ": ", name, " must be ", dtype,
+              ", got ", t.scalar_type());
+  TORCH_CHECK(t.dim() == dim, op, ": ", name, " must be ", dim, "-D");
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
 torch::Tensor moe_gather_rows(
     torch::Tensor src, torch::Tensor idx,
     c10::optional<torch::Tensor> scale) {
-  TORCH_CHECK(src.is_cuda() && src.scalar_type() == torch::kBFloat16 && src.is_contiguous());
-  TORCH_CHECK(idx.scalar_type() == torch::kInt64);
+  check_moe_arg(src, torch::kBFloat16, 2, "moe_gather_rows", "src");
+  check_moe_arg(idx, torch::kInt64, 1, "moe_gather_rows", "idx");
+  if (scale.has_value()) {
+    check_moe_arg(*scale, torch::kFloat32, 1, "moe_gather_rows", "scale");
+    TORCH_CHECK(scale->numel() == idx.numel(),
+                "moe_gather_rows: scale must have one entry per output row");
+  }
   const int64_t R = idx.numel(), H = src.size(1);
   auto out = torch::empty({R, H}, src.options());
   if (R == 0) return out;
@@ -132,14 +148,23 @@ torch::Tensor moe_gather_rows(
 torch::Tensor moe_csr_combine(
     torch::Tensor expert_out, c10::optional<torch::Tensor> probs,
     torch::Tensor inv, int64_t T, int64_t K) {
-  TORCH_CHECK(expert_out.is_cuda() && expert_out.scalar_type() == torch::kBFloat16);
+  check_moe_arg(expert_out, torch::kBFloat16, 2, "moe_csr_combine", "expert_out");
+  check_moe_arg(inv, torch::kInt64, 1, "moe_csr_combine", "inv");
+  const int64_t R = expert_out.size(0);
+  TORCH_CHECK(T >= 0 && K >= 1 && T * K == R && inv.numel() == R,
+              "moe_csr_combine: expected T*K == rows(expert_out) == len(inv)");
+  if (probs.has_value()) {
+    check_moe_arg(*probs, torch::kFloat32, 1, "moe_csr_combine", "probs");
+    TORCH_CHECK(probs->numel() == R,
+                "moe_csr_combine: probs must have one entry per expert row");
+  }
   const int64_t H = expert_out.size(1);
   auto out = torch::empty({T, H}, expert_out.options());
   if (T == 0) return out;
   auto stream = at::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(
       d9d::csr_combine_kernel, dim3((unsigned)T), dim3(64), 0, stream,
-      reinterpret_cast<const __bf16*>(expert_out.contiguous().data_ptr()),
+      reinterpret_cast<const __bf16*>(expert_out.data_ptr()),
       probs ? probs->data_ptr<float>() : nullptr,
       inv.data_ptr<int64_t>(),
       reinterpret_cast<__bf16*>(out.data_ptr()), T, H, (int)K);
@@ -148,14 +173,21 @@ torch::Tensor moe_csr_combine(
 
 torch::Tensor moe_row_dot(
     torch::Tensor grad_out, torch::Tensor expert_out, torch::Tensor row_to_token) {
+  check_moe_arg(grad_out, torch::kBFloat16, 2, "moe_row_dot", "grad_out");
+  check_moe_arg(expert_out, torch::kBFloat16, 2, "moe_row_dot", "expert_out");
+  check_moe_arg(row_to_token, torch::kInt64, 1, "moe_row_dot", "row_to_token");
+  TORCH_CHECK(grad_out.size(1) == expert_out.size(1),
+              "moe_row_dot: grad_out and expert_out hidden sizes differ");
+  TORCH_CHECK(row_to_token.numel() == expert_out.size(0),
+              "moe_row_dot: row_to_token must have one entry per expert row");
   const int64_t R = expert_out.size(0), H = expert_out.size(1);
   auto dprobs = torch::empty({R}, grad_out.options().dtype(torch::kFloat32));
   if (R == 0) return dprobs;
   auto stream = at::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(
       d9d::row_dot_kernel, dim3((unsigned)R), dim3(64), 0, stream,
-      reinterpret_cast<const __bf16*>(grad_out.contiguous().data_ptr()),
-      reinterpret_cast<const __bf16*>(expert_out.contiguous().data_ptr()),
+      reinterpret_cast<const __bf16*>(grad_out.data_ptr()),
+      reinterpret_cast<const __bf16*>(expert_out.data_ptr()),
       row_to_token.data_ptr<int64_t>(),
       dprobs.data_ptr<float>(), R, H);
   return dprobs;

@@ -218,11 +218,20 @@ __global__ void router_topk_bwd_kernel(
 std::vector<torch::Tensor> router_topk_fwd(
     torch::Tensor logits, c10::optional<torch::Tensor> bias, int64_t K,
     bool renormalize) {
-  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kFloat32 &&
-              logits.is_contiguous());
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous(),
+              "router_topk_fwd: logits must be a contiguous (T, E) GPU tensor");
+  TORCH_CHECK(logits.scalar_type() == torch::kFloat32,
+              "router_topk_fwd: logits must be fp32, got ", logits.scalar_type());
   const int64_t T = logits.size(0);
   const int E = logits.size(1);
   TORCH_CHECK(E <= 1024 && K <= 16, "router kernel supports E<=1024, k<=16");
+  // beyond E the argmax would pick the padding lanes (indices >= E)
+  TORCH_CHECK(K >= 1 && K <= E, "router_topk_fwd: top_k=", K,
+              " must be in [1, E=", E, "]");
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->numel() == E,
+                "router_topk_fwd: bias must be an (E,) GPU tensor");
+  }
   auto top_probs = torch::empty({T, K}, logits.options());
   auto top_idx = torch::empty({T, K}, logits.options().dtype(torch::kInt64));
   if (T == 0) return {top_probs, top_idx};
@@ -246,9 +255,21 @@ std::vector<torch::Tensor> router_topk_fwd(
 torch::Tensor router_topk_bwd(
     torch::Tensor logits, torch::Tensor top_idx, torch::Tensor dtop,
     bool renormalize) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous() &&
+                  logits.scalar_type() == torch::kFloat32,
+              "router_topk_bwd: logits must be a contiguous fp32 (T, E) GPU tensor");
+  TORCH_CHECK(top_idx.is_cuda() && top_idx.scalar_type() == torch::kInt64 &&
+                  top_idx.is_contiguous() && top_idx.dim() == 2 &&
+                  top_idx.size(0) == logits.size(0),
+              "router_topk_bwd: top_idx must be a contiguous int64 (T, K) GPU tensor");
+  TORCH_CHECK(dtop.is_cuda() && dtop.scalar_type() == torch::kFloat32 &&
+                  dtop.sizes() == top_idx.sizes(),
+              "router_topk_bwd: dtop must be fp32 with the shape of top_idx");
   const int64_t T = logits.size(0);
   const int E = logits.size(1);
   const int K = top_idx.size(1);
+  TORCH_CHECK(E <= 1024 && K <= 16 && K <= E,
+              "router kernel supports E<=1024, k<=min(16, E)");
   auto dlogits = torch::empty_like(logits);
   if (T == 0) return dlogits;
   constexpr int kBlock = 256;

@@ -83,26 +83,37 @@ class _FlashAttnFunction(torch.autograd.Function):
         ctx.window_left = window_left
         ctx.q_offset = q_offset
         ctx.has_sinks = sinks is not None
+        # unused output grads arrive as None, so the common out-only loss
+        # pays nothing for the differentiable lse
+        ctx.set_materialize_grads(False)
         return out, lse
 
     @staticmethod
     def backward(ctx, dout, dlse):
         q, k, v, out, lse = ctx.saved_tensors[:5]
+        if dout is None:
+            dout = torch.zeros_like(out)
         ext = get_ext()
         # The sink only enters through the LSE, which the kernel reads back:
-        # dq/dk/dv formulas are unchanged.
+        # dq/dk/dv formulas are unchanged. lse is a differentiable output:
+        # d(lse)/dS = P, so dS = P*(dP - delta) + P*dlse (the kernel folds
+        # dlse into delta).
+        dlse = dlse.float().contiguous() if dlse is not None else None
         dq, dk, dv = ext.flash_attn_bwd(
             dout.contiguous(), q.contiguous(), k.contiguous(), v.contiguous(),
             out.contiguous(), lse, None, None,
-            ctx.causal, ctx.softmax_scale, ctx.window_left, ctx.q_offset,
+            ctx.causal, ctx.softmax_scale, ctx.window_left, ctx.q_offset, dlse,
         )
         dsinks = None
         if ctx.has_sinks:
             sinks = ctx.saved_tensors[5]
-            # p_sink(b,h,t) = exp(sink_h - lse); dsink_h = -sum p_sink * delta
+            # p_sink(b,h,t) = exp(sink_h - lse);
+            # dsink_h = sum p_sink * (dlse - delta)
             # with delta = rowsum(dout * out) (analytic sink grad, reference
             # d9d/kernel/flash_attn/function.py dsink).
             delta = (out.float() * dout.float()).sum(-1).permute(0, 2, 1)  # (B,Hq,S)
+            if dlse is not None:
+                delta = delta - dlse
             p_sink = torch.exp(sinks.float().view(1, -1, 1) - lse)
             dsinks = -(p_sink * delta).sum(dim=(0, 2)).to(sinks.dtype)
         return dq, dk, dv, dsinks, None, None, None, None
@@ -191,21 +202,29 @@ class _FlashAttnVarlenFunction(torch.autograd.Function):
         ctx.softmax_scale = softmax_scale
         ctx.window_left = window_left
         ctx.has_sinks = sinks is not None
+        # unused output grads arrive as None, so the common out-only loss
+        # pays nothing for the differentiable lse
+        ctx.set_materialize_grads(False)
         return out, lse
 
     @staticmethod
     def backward(ctx, dout, dlse):
         q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors[:7]
+        if dout is None:
+            dout = torch.zeros_like(out)
         ext = get_ext()
+        dlse = dlse.float().contiguous() if dlse is not None else None
         dq, dk, dv = ext.flash_attn_bwd(
             dout.contiguous(), q.contiguous(), k.contiguous(), v.contiguous(),
             out.contiguous(), lse, cu_q, cu_k,
-            ctx.causal, ctx.softmax_scale, ctx.window_left, 0,
+            ctx.causal, ctx.softmax_scale, ctx.window_left, 0, dlse,
         )
         dsinks = None
         if ctx.has_sinks:
             sinks = ctx.saved_tensors[7]
             delta = (out.float() * dout.float()).sum(-1).permute(1, 0)  # (Hq,total)
+            if dlse is not None:
+                delta = delta - dlse
             p_sink = torch.exp(sinks.float().view(-1, 1) - lse)
             dsinks = -(p_sink * delta).sum(dim=1).to(sinks.dtype)
         return dq, dk, dv, None, None, dsinks, None, None, None

@@ -62,15 +62,24 @@ def _chunk_fwd(e32, c, targets, vocab_start, softcap=None):
     return lse, tgt_logit
 
 
-def _kernel_forward(e, c, targets, vocab_start):
-    """Fused CDNA4 forward: one kernel computes per-token lse + target logit."""
+def _kernel_forward(e, c, targets, vocab_start, with_bwd_lse=False):
+    """Fused CDNA4 forward: one kernel computes per-token lse + target logit.
+
+    `with_bwd_lse` also returns the lse of the logits ROUNDED TO bf16. The
+    backward recomputes the logits as a bf16 GEMM output, and
+    exp(bf16 logit - lse) is a distribution (sums to 1 over the row) only
+    against that lse; against the fp32 one every p carries the rounding error
+    of its own logit, 3% at |logit| in [8, 16).
+    """
 
     local_targets = (targets - vocab_start).clamp(min=-1)  # out-of-shard -> -1
-    lse, tgt = get_ext().cce_fwd(e.contiguous(), c.contiguous(), local_targets)
+    lse, tgt, lse_bf = get_ext().cce_fwd(e.contiguous(), c.contiguous(), local_targets)
     in_shard = (targets - vocab_start >= 0) & (targets - vocab_start < c.shape[0]) & (
         targets != LM_IGNORE_INDEX
     )
     tgt_logit = torch.where(in_shard, tgt, torch.zeros_like(tgt))
+    if with_bwd_lse:
+        return lse, tgt_logit, lse_bf
     return lse, tgt_logit
 
 
@@ -91,8 +100,11 @@ class _LinearCrossEntropyFunction(torch.autograd.Function):
     def forward(ctx, e, c, targets, vp_group, vocab_start, vocab_end, filter_eps, softcap):
         T = e.shape[0]
         if softcap is None and _can_use_kernel(e, c):
-            lse, tgt_logit = _kernel_forward(e, c, targets, vocab_start)
+            lse, tgt_logit, lse_bwd = _kernel_forward(e, c, targets, vocab_start, True)
         else:
+            # the chunked path takes its lse from the logits the backward
+            # recomputes (same dtype, same rounding): one lse serves both
+            lse_bwd = None
             lse_parts = []
             tgt_parts = []
             for s in range(0, T, _ROW_CHUNK):
@@ -106,18 +118,24 @@ class _LinearCrossEntropyFunction(torch.autograd.Function):
         if vp_group is not None:
             # Merge lse across vocab shards: lse_full = log sum_r exp(lse_r).
             world = dist.get_world_size(vp_group)
+            # (lse, lse_bwd) travel in one gather
+            local = lse if lse_bwd is None else torch.stack([lse, lse_bwd])
             all_lse = torch.empty(
-                world * lse.numel(), dtype=lse.dtype, device=lse.device
+                world * local.numel(), dtype=lse.dtype, device=lse.device
             )
-            dist.all_gather_into_tensor(all_lse, lse.contiguous(), group=vp_group)
-            lse = torch.logsumexp(all_lse.view(world, -1), dim=0)
+            dist.all_gather_into_tensor(all_lse, local.contiguous(), group=vp_group)
+            merged = torch.logsumexp(all_lse.view(world, -1), dim=0)
+            if lse_bwd is None:
+                lse = merged
+            else:
+                lse, lse_bwd = merged.view(2, -1).unbind(0)
             dist.all_reduce(tgt_logit, group=vp_group)
 
         loss = lse - tgt_logit  # = -log p(target)
         ignored = targets == LM_IGNORE_INDEX
         loss = torch.where(ignored, torch.zeros_like(loss), loss)
 
-        ctx.save_for_backward(e, c, targets, lse)
+        ctx.save_for_backward(e, c, targets, lse if lse_bwd is None else lse_bwd)
         ctx.vp = (vp_group, vocab_start, vocab_end)
         ctx.filter_eps = filter_eps
         ctx.softcap = softcap
@@ -235,8 +253,11 @@ def linear_cross_entropy(
     API mirrors the reference wrapper (d9d/kernel/cce/main.py): `shift` rolls
     targets left by 1 (or `shift` positions) for causal LMs; `reduction` in
     {"none", "mean", "sum"} ("mean" averages over non-ignored tokens);
-    `filter_eps` zeroes negligible non-target probabilities in the backward
-    ("auto" = bf16-epsilon-scaled threshold, None/0 disables). `return_lse`
+    `filter_eps` zeroes non-target probabilities p < eps in the backward
+    ("auto" = 2**-12, about the bf16 rounding step; None/0 disables). The
+    filter is applied ON THE HIP KERNEL PATH ONLY (bf16 CUDA inputs without
+    softcap): the eager path (CPU, fp32, softcap) ignores it and always
+    returns the unfiltered gradient. `return_lse`
     additionally returns the per-token logsumexp as a DIFFERENTIABLE output.
     `softcap` applies cap * tanh(logit / cap) before the softmax.
     """

@@ -17,7 +17,8 @@ from ._ext import get_ext, has_ext
 
 
 def _use_kernels(t: torch.Tensor) -> bool:
-    return t.is_cuda and has_ext()
+    # the kernels are bf16-only; other dtypes take the index-op path
+    return t.is_cuda and t.dtype == torch.bfloat16 and has_ext()
 
 
 class _GatherRowsFunction(torch.autograd.Function):

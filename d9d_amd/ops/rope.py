@@ -12,9 +12,12 @@ from ._ext import get_ext, has_ext
 class _RopeQKFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, cos, sin):
+        # save what the kernel saw: an expanded (batch-broadcast) cos/sin is
+        # not contiguous and the backward launch needs the same layout
+        cos, sin = cos.contiguous(), sin.contiguous()
         ctx.save_for_backward(cos, sin)
         q_out, k_out = get_ext().rope_qk(
-            q.contiguous(), k.contiguous(), cos.contiguous(), sin.contiguous(), 1.0
+            q.contiguous(), k.contiguous(), cos, sin, 1.0
         )
         return q_out, k_out
 

@@ -50,9 +50,15 @@ def router_topk(
 
     `bias` participates in the top-k *selection* only (aux-free load
     balancing) and carries no gradient."""
+    if top_k > logits.shape[-1]:
+        raise ValueError(
+            f"router_topk: top_k={top_k} exceeds the number of experts "
+            f"({logits.shape[-1]})"
+        )
     if (
         logits.is_cuda
         and has_ext()
+        and logits.dtype == torch.float32
         and logits.shape[-1] <= 1024
         and top_k <= 16
     ):

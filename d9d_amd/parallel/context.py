@@ -76,7 +76,7 @@ def _block_bwd(q, k, v, out_final, dout, lse_merged, causal_block: bool, scale: 
         dq, dk, dv = get_ext().flash_attn_bwd(
             dout.contiguous(), q.contiguous(), k.contiguous(), v.contiguous(),
             out_final.contiguous(), lse_merged.contiguous(), None, None,
-            causal_block, scale, -1, 0,
+            causal_block, scale, -1, 0, None,
         )
         return dq, dk, dv
 
