@@ -16,19 +16,12 @@
 // falls back to the chunked rocBLAS path above that). Backward stays the
 // chunked-GEMM path (cce.py) — it is GEMM-shaped and rocBLAS-efficient.
 #include "common.h"
+#include "mfma.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 namespace d9d {
-
-typedef __bf16 bf16_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-D9D_DEVICE f32x4 mfma16c(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 constexpr float kLog2eC = 1.44269504088896340736f;
 
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
             ((ks * 32 + (lane >> 4) * 8) * 2) ^ ((vrow & kSwz) << 4);
         const bf16x8 cb = *reinterpret_cast<const bf16x8*>(
             reinterpret_cast<const char*>(c_lds) + vrow * (KT * 2) + cbyte);
-        acc[nt] = mfma16c(ea, cb, acc[nt]);
+        acc[nt] = mfma16(ea, cb, acc[nt]);
       }
     }
     __builtin_amdgcn_s_setprio(0);

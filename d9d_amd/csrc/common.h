@@ -117,4 +117,35 @@ __host__ __device__ __forceinline__ int64_t ceil_div(int64_t a, int64_t b) {
   return (a + b - 1) / b;
 }
 
+// ---- XCD-aware work mapping ---------------------------------------------------
+
+// The hardware deals linear workgroup ids round-robin over the 8 XCDs
+// (accelerator dies, each with a private L2): id `lin` runs on XCD lin & 7 as
+// that die's (lin >> 3)-th workgroup. This bijection of [0, nwg) hands XCD x a
+// CONTIGUOUS span of work ids instead -- the first nwg % 8 dies get
+// nwg / 8 + 1 ids, the rest nwg / 8 -- so neighbouring work items, which
+// share operands, re-read them from one die's L2 instead of every die
+// streaming them from HBM.
+constexpr __host__ __device__ int xcd_remap(int lin, int nwg) {
+  const int xcd = lin & 7;
+  const int q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+}
+
+constexpr bool xcd_remap_is_permutation() {
+  // fewer workgroups than XCDs, exact multiples of 8, and remainders
+  constexpr int kCases[] = {1, 7, 8, 9, 61, 64};
+  for (int nwg : kCases) {
+    bool seen[64] = {};
+    for (int lin = 0; lin < nwg; ++lin) {
+      const int wid = xcd_remap(lin, nwg);
+      if (wid < 0 || wid >= nwg || seen[wid]) return false;
+      seen[wid] = true;
+    }
+  }
+  return true;
+}
+static_assert(xcd_remap_is_permutation(),
+              "xcd_remap must be a permutation of [0, nwg)");
+
 }  // namespace d9d

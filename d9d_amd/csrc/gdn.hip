@@ -16,19 +16,12 @@
 //    (document, head) from a zero state, conv taps clipped at the
 //    document start. cu_seqlens is validated on the host before launch.
 #include "common.h"
+#include "mfma.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 namespace d9d {
-
-typedef __bf16 bf16_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-D9D_DEVICE f32x4 mfma16gdn(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 // ---------------------------------------------------------------------------
 // causal depthwise conv (kernel <= 4) + SiLU, bf16
@@ -157,11 +150,9 @@ __global__ void causal_conv_silu_bwd_kernel(
 //   O       = (e^{gc} Q) @ S + N @ R                      (MFMA, R as bf16)
 //   S       = e^{gc_last} S + (K e^{gc_last-gc})^T @ R    (fp32 VALU)
 //
-// MFMA fragment map (verified by attention.hip's mfma_selfcheck):
-//   mfma16gdn(a, b, acc): A[m][k] lane m = l&15, k-slice (l>>4)*8;
-//   B[k][n] lane n = l&15, same k-slice; C[m][n] lane: m = (l>>4)*4 + r,
-//   n = l&15. All tiles here are row-major [row][64] so A fragments are
-//   contiguous row reads; B fragments read the row of the TRANSPOSED
+// MFMA fragment map: see mfma.h (verified by attention.hip's
+//   mfma_selfcheck). All tiles here are row-major [row][64] so A fragments
+//   are contiguous row reads; B fragments read the row of the TRANSPOSED
 //   operand copy (kc rows for K^T, sbT rows for S, rbT rows for R).
 
 constexpr int kGdnC = 64;   // chunk rows
@@ -335,7 +326,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
         for (int nt = 0; nt < 4; ++nt) {
           const int brow = nt * 16 + (lane & 15);   // B = K^T: col j = K row j
           const bf16x8 b = *reinterpret_cast<const bf16x8*>(&L.kc[brow][d0]);
-          acc[nt] = mfma16gdn(a, b, acc[nt]);
+          acc[nt] = mfma16(a, b, acc[nt]);
         }
       }
 #pragma unroll
@@ -379,7 +370,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
         for (int nt = 0; nt < NTV; ++nt) {
           const int vcol = nt * 16 + (lane & 15);
           const bf16x8 b = *reinterpret_cast<const bf16x8*>(&L.sbT[vcol][d0]);
-          acc[nt] = mfma16gdn(a, b, acc[nt]);
+          acc[nt] = mfma16(a, b, acc[nt]);
         }
       }
 #pragma unroll
@@ -469,7 +460,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
           for (int nt = 0; nt < 4; ++nt) {
             const int brow = nt * 16 + (lane & 15);
             const bf16x8 b = *reinterpret_cast<const bf16x8*>(&L.kc[brow][d0]);
-            acc[nt] = mfma16gdn(a, b, acc[nt]);
+            acc[nt] = mfma16(a, b, acc[nt]);
           }
         }
   #pragma unroll
@@ -502,7 +493,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
           for (int nt = 0; nt < NTV; ++nt) {
             const int vcol = nt * 16 + (lane & 15);
             const bf16x8 b = *reinterpret_cast<const bf16x8*>(&L.sbT[vcol][d0]);
-            acc[nt] = mfma16gdn(a, b, acc[nt]);
+            acc[nt] = mfma16(a, b, acc[nt]);
           }
         }
         // + N @ R  (k dim = chunk rows j, 64 wide)
@@ -514,7 +505,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
           for (int nt = 0; nt < NTV; ++nt) {
             const int vcol = nt * 16 + (lane & 15);
             const bf16x8 b = *reinterpret_cast<const bf16x8*>(&L.rbT[vcol][j0]);
-            acc[nt] = mfma16gdn(a, b, acc[nt]);
+            acc[nt] = mfma16(a, b, acc[nt]);
           }
         }
   #pragma unroll
@@ -712,8 +703,8 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
         for (int nt = 0; nt < 4; ++nt) {
           const int brow = nt * 16 + (lane & 15);
           const bf16x8 b = *reinterpret_cast<const bf16x8*>(&L.kc[brow][d0]);
-          accm[nt] = mfma16gdn(ak, b, accm[nt]);
-          accn[nt] = mfma16gdn(aq, b, accn[nt]);
+          accm[nt] = mfma16(ak, b, accm[nt]);
+          accn[nt] = mfma16(aq, b, accn[nt]);
         }
       }
 #pragma unroll
@@ -763,8 +754,8 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
           const int dv = nt * 16 + (lane & 15);
           const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(&L.dsT[dv][d0]);
           const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(&L.doT[dv][d0]);
-          acc[nt] = mfma16gdn(aw, b1, acc[nt]);
-          acc[nt] = mfma16gdn(an, b2, acc[nt]);
+          acc[nt] = mfma16(aw, b1, acc[nt]);
+          acc[nt] = mfma16(an, b2, acc[nt]);
         }
       }
       // wait: nbT rows are A fragments over k = t (the q-row index) —

@@ -27,6 +27,7 @@
 // kernels stage with global_load_lds behind counted vmcnt waits; the
 // fallbacks stage through registers (T14) and take any K and N.
 #include "common.h"
+#include "mfma.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -37,15 +38,6 @@
 #include <type_traits>
 
 namespace d9d {
-
-typedef __bf16 bf16_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-D9D_DEVICE f32x4 mfma16g(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 constexpr int kBM = 256;
 constexpr int kBN = 192;
@@ -62,15 +54,9 @@ struct WorkItem {
 D9D_DEVICE WorkItem locate_work(const int* __restrict__ row_off,
                                 const int* __restrict__ mtile_pref,
                                 int E, int n_tiles, int bn) {
-  // XCD-aware work mapping: hardware deals linear block ids round-robin over
-  // the 8 XCDs (each with a private L2). The bijective remap gives each XCD a
-  // CONTIGUOUS span of expert-major work items, so one expert's weight slice
-  // and A rows are re-read from that XCD's L2 instead of HBM.
-  const int nwg = gridDim.x;
-  const int xcd = blockIdx.x & 7;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int wid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q)
-                  + (blockIdx.x >> 3);
+  // Each XCD gets a contiguous span of expert-major work items, so one
+  // expert's weight slice and A rows are re-read from that XCD's L2.
+  const int wid = xcd_remap(blockIdx.x, gridDim.x);
   // work id -> (expert, m_tile) via binary search in the m-tile prefix
   const int mt_global = wid / n_tiles;
   int lo = 0, hi = E - 1;
@@ -341,7 +327,7 @@ __global__ __launch_bounds__(512, 1) void gmm_staged_kernel(
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) acc[i][j] = mfma16g(a_frag[i], b_frag[j], acc[i][j]);
+        for (int j = 0; j < 3; ++j) acc[i][j] = mfma16(a_frag[i], b_frag[j], acc[i][j]);
     }
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();
@@ -573,7 +559,7 @@ __global__ __launch_bounds__(512, 1) void gmm_8phase_kernel(
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks)
             acc[2 * p + il][j] =
-                mfma16g(a_frag[il][ks], b_frag[j][ks], acc[2 * p + il][j]);
+                mfma16(a_frag[il][ks], b_frag[j][ks], acc[2 * p + il][j]);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_s_barrier();
     }
@@ -604,7 +590,7 @@ __global__ __launch_bounds__(512, 1) void gmm_8phase_kernel(
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
           acc[2 * p + il][j] =
-              mfma16g(a_frag_t[il], b_frag_t[j], acc[2 * p + il][j]);
+              mfma16(a_frag_t[il], b_frag_t[j], acc[2 * p + il][j]);
       __builtin_amdgcn_s_setprio(0);
     }
   }
@@ -775,7 +761,7 @@ __global__ __launch_bounds__(512, 1) void gmm_db_8phase_kernel(
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks)
             acc[2 * p + il][j] =
-                mfma16g(a_frag[il][ks], b_frag[j][ks], acc[2 * p + il][j]);
+                mfma16(a_frag[il][ks], b_frag[j][ks], acc[2 * p + il][j]);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_s_barrier();
     }
@@ -833,11 +819,7 @@ __global__ __launch_bounds__(512, 1) void gmm_db_kernel(
   // into registers early (overlapping the previous chunk's MFMAs) with
   // branchless clamped addresses, transposed into LDS with 8-byte writes
   // late. Rows past r_end are zero-filled (they enter the row-sum).
-  union u64u {
-    uint64_t u;
-    ushort s[4];
-  };
-  u64u a_c0[4], a_c1[4], g_c0[4], g_c1[4];
+  bf16x4_bits a_c0[4], a_c1[4], g_c0[4], g_c1[4];
 
   auto load_regs = [&](int rt) {
 #pragma unroll
@@ -914,7 +896,7 @@ __global__ __launch_bounds__(512, 1) void gmm_db_kernel(
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16g(a_frag[i], g_frag[j], acc[i][j]);
+        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(a_frag[i], g_frag[j], acc[i][j]);
     }
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();
