@@ -6,9 +6,11 @@
 //   * Forward: workgroup = 4 waves x 32 q-rows (two 16-row m-tiles per wave,
 //     q block 128), KV tiles of 64 staged with the T14 issue-early/write-late
 //     split — K row-major with an XOR swizzle (conflict-free ds_read_b128
-//     B-fragments), V transposed with vectorized 8-byte LDS writes. Online
-//     softmax in fp32; s_setprio(1) around MFMA clusters; LSE written for
-//     context-parallel merging.
+//     fragments), V transposed with vectorized 8-byte LDS writes. It
+//     computes the transposed products S^T = K Q^T and O^T = V^T P^T, so a
+//     lane's values all belong to one q row: online softmax in fp32 per
+//     lane, P stays in registers. s_setprio(1) around MFMA clusters; LSE
+//     written for context-parallel merging.
 //   * Backward: FA2 decomposition; workgroup = 8 waves owning a 128-row KV
 //     tile, looping q tiles (Q/dO prefetched into registers under the MFMAs,
 //     transposed images derived LDS-to-LDS); dK/dV accumulate in registers,
@@ -107,6 +109,34 @@ D9D_DEVICE void load_transposed_block(
   }
 }
 
+// Which kv row of a 64-row tile LDS row p of the forward's K tile holds. The
+// forward feeds the C registers of S^T = K Q^T straight back as the B operand
+// of O^T = V^T P^T: B slot (g, j) of PV k-step b (32 kv) is filled from C
+// register j & 3 of lane group g of score tile 2b + (j >> 2), i.e. from K
+// tile row p = 32b + 16(j >> 2) + 4g + (j & 3), and must carry
+// kv = 32b + 8g + j, the kv that V^T presents there in its natural order.
+// So row p = 32b + 16h + 4g + i is loaded with kv row 32b + 8g + 4h + i.
+constexpr int pv_pos(int p) {
+  return (p & ~31) | ((p & 12) << 1) | ((p & 16) >> 2) | (p & 3);
+}
+
+constexpr bool pv_pos_is_unit_permutation() {
+  bool seen[64] = {};
+  for (int p = 0; p < 64; ++p) {
+    const int kv = pv_pos(p);
+    if (kv < 0 || kv >= 64 || seen[kv]) return false;
+    seen[kv] = true;
+    // aligned 4-row groups map to aligned 4-row groups, in order
+    if (kv != pv_pos(p & ~3) + (p & 3) || pv_pos(p & ~3) % 4 != 0) return false;
+    // B slot (g, j) of k-step b, packed from row p's C register, carries kv
+    const int b = kv >> 5, g = (kv >> 3) & 3, j = kv & 7;
+    if (p != 32 * b + 16 * (j >> 2) + 4 * g + (j & 3)) return false;
+  }
+  return true;
+}
+static_assert(pv_pos_is_unit_permutation(),
+              "pv_pos must permute 0..63 in aligned 4-row units");
+
 template <int D, int ROWS>
 D9D_DEVICE void store_transposed_block(
     bf16_t* dst, const bf16x4_bits& c0, const bf16x4_bits& c1, int idx) {
@@ -172,7 +202,10 @@ D9D_DEVICE TileLoc locate_tile(
     const int bh = wid / gridDim.x;
     t.b = bh / Hq;
     t.h = bh % Hq;
-    t.tile = wid % gridDim.x;
+    // Heavy first: a causal q-tile's work grows with its index (the forward)
+    // and shrinks with its kv-tile's (the backward), so the forward walks
+    // its tiles backwards and no XCD ends on a head's longest tiles.
+    t.tile = TILE_KV ? wid % gridDim.x : gridDim.x - 1 - wid % gridDim.x;
     t.q_lo = 0; t.Sq_loc = Sq; t.kv_lo = 0; t.Skv_loc = Skv;
     t.causal_off = q_offset;
     t.valid = true;
@@ -211,13 +244,16 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
   constexpr int kKS = D / 32;   // k-steps over head dim
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* k_lds = reinterpret_cast<bf16_t*>(smem);   // [kFwdKv][D] swizzled
+  // [kFwdKv][D] swizzled, row p = kv row pv_pos(p); fwd_smem_bytes() is this
+  // carve-up
+  bf16_t* k_lds = reinterpret_cast<bf16_t*>(smem);
   bf16_t* vt_lds = k_lds + kFwdKv * D;               // [D][kFwdKv] transposed
-  // per-wave P scratch: [4][32][kFwdKv+8]; fwd_smem_bytes() is this carve-up
-  bf16_t* p_lds = vt_lds + D * kFwdKv;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
+  const int lrow = lane & 15;  // the q row (of a 16-row sub-tile) this lane owns
+  const int lgrp = lane >> 4;
+  const bool upper = lane >= 32;
 
   // one (b, h)'s q-tiles share its KV stream (XCD grouping)
   const TileLoc loc = locate_tile<kFwdQ, false>(
@@ -232,16 +268,21 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
   const int64_t q_row_stride = (int64_t)Hq * D;
   const int64_t kv_row_stride = (int64_t)Hkv * D;
 
-  // ---- load this wave's 32 q rows (2 m-tiles) into A fragments -------------
+  // ---- load this wave's 32 q rows (2 sub-tiles) into fragments -------------
+  // The kernel computes the TRANSPOSED products S^T = K Q^T and
+  // O^T = V^T P^T: Q is the B operand, and in the C layout of S^T and O^T
+  // every value a lane holds belongs to ONE q row (lane & 15). The row
+  // statistics are then per lane, and the S^T registers are already a legal
+  // B operand for PV (see pv_pos): P never leaves the registers.
   bf16x8 q_frag[2][kKS];
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
-    const int q_row_local = q_tile * kFwdQ + wave * 32 + m * 16 + (lane & 15);
+    const int q_row_local = q_tile * kFwdQ + wave * 32 + m * 16 + lrow;
     const int safe_row = q_lo + min(q_row_local, Sq_loc - 1);
     const bf16_t* qp = q + q_base + (int64_t)safe_row * q_row_stride;
 #pragma unroll
     for (int ks = 0; ks < kKS; ++ks) {
-      q_frag[m][ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32 + (lane >> 4) * 8);
+      q_frag[m][ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32 + lgrp * 8);
     }
   }
 
@@ -249,18 +290,17 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
   // sinks[h] and no value row: seed the running max/sum with it and the
   // online softmax (and the LSE the backward reads) absorbs it for free.
   const float m_init = sinks ? sinks[h] : -1e30f;
-  // l is tracked per lane and merged at the epilogue: seed the sink's
-  // softmax column on ONE lane of each row group only
-  const float l_init = (sinks && (threadIdx.x & 15) == 0) ? 1.f : 0.f;
-  float m_run[2][4], l_run[2][4];
+  // l is kept as partial sums per kv column class (see the loop), merged at
+  // the epilogue: seed the sink's column on class 0 only
+  const float l_init = (sinks && lgrp == 0) ? 1.f : 0.f;
+  float m_run[2], l_run[2][4];
 #pragma unroll
-  for (int m = 0; m < 2; ++m)
+  for (int m = 0; m < 2; ++m) {
+    m_run[m] = m_init;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      m_run[m][r] = m_init;
-      l_run[m][r] = l_init;
-    }
-  f32x4 o_acc[2][kNT];
+    for (int r = 0; r < 4; ++r) l_run[m][r] = r == 0 ? l_init : 0.f;
+  }
+  f32x4 o_acc[2][kNT];  // O^T: lane holds O[q = lrow][d = nt*16 + lgrp*4 + r]
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -287,7 +327,7 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
       const int idx = (threadIdx.x + it * 256) * 8;
       const int row = idx / D;
       const int col = idx % D;
-      const int g_row = kv_lo + min(kv0 + row, Skv_loc - 1);
+      const int g_row = kv_lo + min(kv0 + pv_pos(row), Skv_loc - 1);
       k_reg[it] = *reinterpret_cast<const bf16x8*>(
           k + kv_base + (int64_t)g_row * kv_row_stride + col);
     }
@@ -321,33 +361,36 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
     const int kv0 = kt * kFwdKv;
     if (kt + 1 < num_kv_tiles) load_regs(kt + 1);  // issue early
 
-    // per m-tile: QK^T -> softmax -> P -> PV
+    // ---- S^T = K Q^T for both q sub-tiles; each K fragment is read once ----
+    // lane holds S[q = lrow][kv = kv0 + pv_pos(nt*16 + lgrp*4 + r)] in
+    // st[m][nt][r]
+    f32x4 st[2][4];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) st[m][nt] = {0.f, 0.f, 0.f, 0.f};
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int kv_row = nt * 16 + lrow;
+#pragma unroll
+      for (int ks = 0; ks < kKS; ++ks) {
+        const int d0 = ks * 32 + lgrp * 8;
+        const bf16x8 ka = *reinterpret_cast<const bf16x8*>(
+            swz_rm_at<D>(reinterpret_cast<char*>(k_lds), kv_row, d0));
+#pragma unroll
+        for (int m = 0; m < 2; ++m) st[m][nt] = mfma16(ka, q_frag[m][ks], st[m][nt]);
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+
+    // ---- per-lane online softmax; P^T packed as PV's B operand -------------
+    bf16x8 pb[2][2];  // [m][ks2]
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-      f32x4 s_acc[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) s_acc[nt] = {0.f, 0.f, 0.f, 0.f};
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const int kv_row = nt * 16 + (lane & 15);
-#pragma unroll
-        for (int ks = 0; ks < kKS; ++ks) {
-          const int d0 = ks * 32 + (lane >> 4) * 8;
-          const bf16x8 kb = *reinterpret_cast<const bf16x8*>(
-              swz_rm_at<D>(reinterpret_cast<char*>(k_lds), kv_row, d0));
-          s_acc[nt] = mfma16(q_frag[m][ks], kb, s_acc[nt]);
-        }
-      }
-      __builtin_amdgcn_s_setprio(0);
-
       const int my_q_row = q_tile * kFwdQ + wave * 32 + m * 16;
-      float p_val[4][4];  // [nt][r]
-      float m_new[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) m_new[r] = m_run[m][r];
       // Tile-level mask skip: most KV tiles sit fully below the causal
-      // diagonal and inside the window for every row of this m-tile -- the
+      // diagonal and inside the window for every row of this sub-tile -- the
       // per-element mask chain (3 compares + select x16) only runs on the
       // diagonal/edge tiles (wave-uniform branch).
       const int row_lo = my_q_row + causal_off;
@@ -356,101 +399,100 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
           (causal && kv0 + kFwdKv - 1 > row_lo) ||
           (window_left >= 0 && kv0 < row_lo + 15 - window_left);
       if (any_mask) {
+        const int row = row_lo + lrow;
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-          const int col = kv0 + nt * 16 + (lane & 15);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int row = my_q_row + (lane >> 4) * 4 + r + causal_off;
-            float s = s_acc[nt][r] * scale;
+            const int col = kv0 + pv_pos(nt * 16 + lgrp * 4 + r);
             const bool masked = causal_window_masked(
                 col >= kv_end, row, col, causal, window_left);
-            p_val[nt][r] = masked ? -1e30f : s;
+            st[m][nt][r] = masked ? -1e30f : st[m][nt][r] * scale;
           }
         }
       } else {
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) p_val[nt][r] = s_acc[nt][r] * scale;
+          for (int r = 0; r < 4; ++r) st[m][nt][r] = st[m][nt][r] * scale;
       }
+      // row max: 16 values in the lane, then the row's 3 other lanes
+      float mx = st[m][0][0];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float mx = fmaxf(fmaxf(p_val[0][r], p_val[1][r]),
-                         fmaxf(p_val[2][r], p_val[3][r]));
+      for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int off = 1; off < 16; off <<= 1) {
-          mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        }
-        m_new[r] = fmaxf(m_new[r], mx);
-      }
-      // l accumulates PER LANE (each lane's own 4 columns): the row-wide
-      // sum only matters at the epilogue, where one 16-lane merge replaces
-      // a 4-step shuffle cascade per row per KV tile (the fwd kernel's
-      // PMC showed a 10:1 VALU:MFMA instruction ratio).
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[m][nt][r]);
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run[m], mx);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          st[m][nt][r] = __builtin_amdgcn_exp2f((st[m][nt][r] - m_new) * kLog2e);
+      // l accumulates per kv column class c = kv & 15, its 4 columns of the
+      // tile added in kv order: the partial sums of the S = Q K^T layout,
+      // where a lane owned one column of each 16-wide tile, so l (and with
+      // it out and lse) keeps its bits. Column c + 16 n sits on lane group
+      // (c >> 3) + 2 (n & 1) in st[2 (n >> 1) + ((c >> 2) & 1)][c & 3]: the
+      // lower lane of a pair (lane ^ 32) sums the classes with c & 4 == 0,
+      // the upper one the others, after one exchange of the halves.
       float l_add[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float acc = 0.f;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          const float p = __builtin_amdgcn_exp2f((p_val[nt][r] - m_new[r]) * kLog2e);
-          p_val[nt][r] = p;
-          acc += p;
-        }
-        l_add[r] = acc;
+        const float give0 = upper ? st[m][0][r] : st[m][1][r];
+        const float give1 = upper ? st[m][2][r] : st[m][3][r];
+        const float got0 = __shfl_xor(give0, 32, 64);
+        const float got1 = __shfl_xor(give1, 32, 64);
+        const float own0 = upper ? st[m][1][r] : st[m][0][r];
+        const float a2 = upper ? got1 : st[m][2][r];
+        const float a3 = upper ? st[m][3][r] : got1;
+        l_add[r] = ((own0 + got0) + a2) + a3;  // n = 0 + 1 commutes
       }
       // Lazy rescale: after the first few KV tiles the running max rarely
       // moves, so alpha == 1 for every row of the wave most of the time --
-      // skip the 4 exp2s and kNT*4 accumulator multiplies (wave-uniform
-      // branch, ~25% of the softmax VALU work).
-      bool same = true;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) same &= (m_new[r] == m_run[m][r]);
-      if (__all(same)) {
+      // skip the exp2 and the kNT*4 accumulator multiplies (wave-uniform
+      // branch).
+      if (__all(m_new == m_run[m])) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) l_run[m][r] += l_add[r];
       } else {
+        const float alpha = __builtin_amdgcn_exp2f((m_run[m] - m_new) * kLog2e);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float alpha = __builtin_amdgcn_exp2f((m_run[m][r] - m_new[r]) * kLog2e);
-          l_run[m][r] = l_run[m][r] * alpha + l_add[r];
-          m_run[m][r] = m_new[r];
+        for (int r = 0; r < 4; ++r) l_run[m][r] = l_run[m][r] * alpha + l_add[r];
+        m_run[m] = m_new;
 #pragma unroll
-          for (int nt = 0; nt < kNT; ++nt) o_acc[m][nt][r] *= alpha;
-        }
+        for (int nt = 0; nt < kNT; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o_acc[m][nt][r] *= alpha;
       }
+      // B slot (lgrp, j) of PV k-step ks2 takes kv = 32 ks2 + 8 lgrp + j: the
+      // registers of st[2 ks2] then st[2 ks2 + 1] (see pv_pos)
+#pragma unroll
+      for (int ks2 = 0; ks2 < 2; ++ks2)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          pb[m][ks2][j] = (bf16_t)st[m][2 * ks2][j];
+          pb[m][ks2][4 + j] = (bf16_t)st[m][2 * ks2 + 1][j];
+        }
+    }
 
-      // P C-layout -> row-major LDS scratch (own-wave slice) -> A fragments
-      {
-        bf16_t* pw = p_lds + (wave * 32 + m * 16) * (kFwdKv + 8);
+    // ---- O^T += V^T P^T; each V^T fragment is read once for both sub-tiles --
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
+    for (int ks2 = 0; ks2 < 2; ++ks2) {
+      const int kv_off = ks2 * 32 + lgrp * 8;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = (lane >> 4) * 4 + r;
-            const int col = nt * 16 + (lane & 15);
-            pw[row * (kFwdKv + 8) + col] = (bf16_t)p_val[nt][r];
-          }
-        }
-        const bf16_t* pr = pw;
-        __builtin_amdgcn_s_setprio(1);
+      for (int nt = 0; nt < kNT; ++nt) {
+        const int d = nt * 16 + lrow;
+        const bf16x8 va = *reinterpret_cast<const bf16x8*>(
+            swz_t_at<kFwdKv>(reinterpret_cast<char*>(vt_lds), d, kv_off));
 #pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2) {
-          const int kv_off = ks2 * 32 + (lane >> 4) * 8;
-          const bf16x8 pa = *reinterpret_cast<const bf16x8*>(
-              pr + (lane & 15) * (kFwdKv + 8) + kv_off);
-#pragma unroll
-          for (int nt = 0; nt < kNT; ++nt) {
-            const int d = nt * 16 + (lane & 15);
-            const bf16x8 vb = *reinterpret_cast<const bf16x8*>(
-                swz_t_at<kFwdKv>(reinterpret_cast<char*>(vt_lds), d, kv_off));
-            o_acc[m][nt] = mfma16(pa, vb, o_acc[m][nt]);
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
+        for (int m = 0; m < 2; ++m) o_acc[m][nt] = mfma16(va, pb[m][ks2], o_acc[m][nt]);
       }
     }
+    __builtin_amdgcn_s_setprio(0);
+
     __syncthreads();
     if (kt + 1 < num_kv_tiles) {
       store_lds();
@@ -458,17 +500,18 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
     }
   }
 
-  // ---- epilogue: merge per-lane l across the 16 column lanes (once),
+  // ---- epilogue: merge the per-lane l across each row's 4 lanes (once),
   // then O /= l; stage in LDS; coalesced 16B stores; LSE --------------------
 #pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        l_run[m][r] += __shfl_xor(l_run[m][r], off, 64);
+  for (int m = 0; m < 2; ++m) {
+    // butterfly over the 16 column classes in the order c ^ 1, 2, 4, 8
+    l_run[m][0] = (l_run[m][0] + l_run[m][1]) + (l_run[m][2] + l_run[m][3]);
+    l_run[m][0] += __shfl_xor(l_run[m][0], 32, 64);
+    l_run[m][0] += __shfl_xor(l_run[m][0], 16, 64);
+  }
   {
-    bf16_t* o_lds = k_lds;  // reuse: [64][D] staged twice (two 64-row halves)
+    // reuse: swizzled [64][D], staged twice (two 64-row halves)
+    char* o_lds = reinterpret_cast<char*>(k_lds);
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       __syncthreads();
@@ -476,15 +519,16 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
       if ((wave >> 1) == half) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
+          const float inv_l = (l_run[m][0] > 0.f) ? 1.f / l_run[m][0] : 0.f;
+          const int row = (wave & 1) * 32 + m * 16 + lrow;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float inv_l = (l_run[m][r] > 0.f) ? 1.f / l_run[m][r] : 0.f;
-            const int row = (wave & 1) * 32 + m * 16 + (lane >> 4) * 4 + r;
+          for (int nt = 0; nt < kNT; ++nt) {
+            bf16x4_bits o4;  // 4 consecutive d of one row
 #pragma unroll
-            for (int nt = 0; nt < kNT; ++nt) {
-              o_lds[row * D + nt * 16 + (lane & 15)] =
-                  (bf16_t)(o_acc[m][nt][r] * inv_l);
-            }
+            for (int r = 0; r < 4; ++r)
+              o4.s[r] = bf16_bits((bf16_t)(o_acc[m][nt][r] * inv_l));
+            *reinterpret_cast<uint64_t*>(
+                swz_rm_at<D>(o_lds, row, nt * 16 + lgrp * 4)) = o4.u;
           }
         }
       }
@@ -497,31 +541,28 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
         if (rg < Sq_loc) {
           *reinterpret_cast<bf16x8*>(
               out + q_base + (int64_t)(q_lo + rg) * q_row_stride + col) =
-              *reinterpret_cast<const bf16x8*>(o_lds + row * D + col);
+              *reinterpret_cast<const bf16x8*>(swz_rm_at<D>(o_lds, row, col));
         }
       }
     }
-    if ((lane & 15) == 0) {
+    if (lgrp == 0) {
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int rg = q_tile * kFwdQ + wave * 32 + m * 16 + (lane >> 4) * 4 + r;
-          if (rg < Sq_loc) {
-            // regular: (B,Hq,Sq); varlen: (Hq,total) with b == 0
-            lse[((int64_t)b * Hq + h) * Sq + q_lo + rg] =
-                m_run[m][r] + __logf(fmaxf(l_run[m][r], 1e-30f));
-          }
+        const int rg = q_tile * kFwdQ + wave * 32 + m * 16 + lrow;
+        if (rg < Sq_loc) {
+          // regular: (B,Hq,Sq); varlen: (Hq,total) with b == 0
+          lse[((int64_t)b * Hq + h) * Sq + q_lo + rg] =
+              m_run[m] + __logf(fmaxf(l_run[m][0], 1e-30f));
         }
       }
     }
   }
 }
 
-// K tile + V^T tile + the P scratch (the kernel's LDS carve-up).
+// K tile + V^T tile (the kernel's LDS carve-up).
 template <int D>
 constexpr size_t fwd_smem_bytes() {
-  return sizeof(bf16_t) * (kFwdKv * D + D * kFwdKv + kFwdQ * (kFwdKv + 8));
+  return sizeof(bf16_t) * (kFwdKv * D + D * kFwdKv);
 }
 
 // ---------------------------------------------------------------------------
@@ -941,6 +982,45 @@ __global__ void mfma_selfcheck_kernel(
   }
 }
 
+// Chained-fragment self-check, the forward's layout argument at its smallest
+// size: X = A1 @ B1 (32x32 @ 32x16) as two 16-row C tiles whose A fragments
+// take A1's rows in pv_pos order; X's C registers, packed as the forward packs
+// P^T, are then the B operand of Y = A2 @ X with A2 (16x32) in natural order.
+__global__ void mfma_chain_selfcheck_kernel(
+    const bf16_t* __restrict__ a1,  // (32, 32) row-major
+    const bf16_t* __restrict__ b1,  // (32, 16) row-major
+    const bf16_t* __restrict__ a2,  // (16, 32) row-major
+    float* __restrict__ y) {        // (16, 16) row-major
+  const int lane = threadIdx.x & 63;
+  bf16x8 bf, a2f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    bf[j] = b1[((lane >> 4) * 8 + j) * 16 + (lane & 15)];
+    a2f[j] = a2[(lane & 15) * 32 + (lane >> 4) * 8 + j];
+  }
+  f32x4 x[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    bf16x8 af;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      af[j] = a1[pv_pos(t * 16 + (lane & 15)) * 32 + (lane >> 4) * 8 + j];
+    }
+    x[t] = mfma16(af, bf, f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+  bf16x8 xb;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    xb[j] = (bf16_t)x[0][j];
+    xb[4 + j] = (bf16_t)x[1][j];
+  }
+  const f32x4 acc = mfma16(a2f, xb, f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    y[((lane >> 4) * 4 + r) * 16 + (lane & 15)] = acc[r];
+  }
+}
+
 // Fused fp32 -> bf16 cast of the three backward accumulators in ONE launch
 // (the three at::native casts measured ~2.6 TB/s and ~0.7 ms per backward at
 // bench shape). Sizes are multiples of 8 (B*S*H*D), so 8-float groups never
@@ -1231,4 +1311,23 @@ torch::Tensor mfma_selfcheck(torch::Tensor a, torch::Tensor b) {
                      reinterpret_cast<const __bf16*>(b.contiguous().data_ptr()),
                      c.data_ptr<float>());
   return c;
+}
+
+torch::Tensor mfma_chain_selfcheck(torch::Tensor a1, torch::Tensor b1,
+                                   torch::Tensor a2) {
+  TORCH_CHECK(a1.sizes() == torch::IntArrayRef({32, 32}));
+  TORCH_CHECK(b1.sizes() == torch::IntArrayRef({32, 16}));
+  TORCH_CHECK(a2.sizes() == torch::IntArrayRef({16, 32}));
+  for (const auto& t : {a1, b1, a2}) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16);
+  }
+  auto a1c = a1.contiguous(), b1c = b1.contiguous(), a2c = a2.contiguous();
+  auto y = torch::empty({16, 16}, a1.options().dtype(torch::kFloat32));
+  auto stream = at::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(d9d::mfma_chain_selfcheck_kernel, dim3(1), dim3(64), 0,
+                     stream, reinterpret_cast<const __bf16*>(a1c.data_ptr()),
+                     reinterpret_cast<const __bf16*>(b1c.data_ptr()),
+                     reinterpret_cast<const __bf16*>(a2c.data_ptr()),
+                     y.data_ptr<float>());
+  return y;
 }

@@ -32,6 +32,7 @@ std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q, t
                                           bool causal, double softmax_scale, int64_t window_left,
                                           int64_t q_offset, c10::optional<torch::Tensor> dlse);
 torch::Tensor mfma_selfcheck(torch::Tensor a, torch::Tensor b);
+torch::Tensor mfma_chain_selfcheck(torch::Tensor a1, torch::Tensor b1, torch::Tensor a2);
 
 // moe_router.hip
 std::vector<torch::Tensor> router_topk_fwd(torch::Tensor logits, c10::optional<torch::Tensor> bias,
@@ -127,6 +128,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_fwd", &flash_attn_fwd, "CDNA4 flash attention forward");
   m.def("flash_attn_bwd", &flash_attn_bwd, "CDNA4 flash attention backward");
   m.def("mfma_selfcheck", &mfma_selfcheck, "MFMA fragment-map self check");
+  m.def("mfma_chain_selfcheck", &mfma_chain_selfcheck,
+        "MFMA chained-fragment (C registers as B operand) self check");
   m.def("rms_norm_fwd", &rms_norm_fwd, "RMSNorm forward (bf16, CDNA4)");
   m.def("rms_norm_bwd", &rms_norm_bwd, "RMSNorm backward (bf16, CDNA4)");
   m.def("silu_mul_fwd", &silu_mul_fwd, "fused silu(a)*b forward");
