@@ -975,6 +975,22 @@ void conv_varlen_checks(const torch::Tensor& x, const torch::Tensor& w) {
   TORCH_CHECK(w.size(1) <= 4, "conv kernel must be <= 4");
 }
 
+// dense conv backward: x, dy (B, S, C) and w (C, K), all bf16 on the device
+void conv_bwd_checks(const torch::Tensor& x, const torch::Tensor& w,
+                     const torch::Tensor& dy) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16,
+              "causal_conv_silu_bwd: x must be a bf16 device tensor");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16,
+              "causal_conv_silu_bwd: w must be a bf16 device tensor");
+  TORCH_CHECK(x.dim() == 3 && w.dim() == 2 && w.size(0) == x.size(2),
+              "causal_conv_silu_bwd: expected x (B, S, C) and w (C, K)");
+  TORCH_CHECK(w.size(1) >= 1 && w.size(1) <= 4,
+              "causal_conv_silu_bwd: conv kernel must be <= 4");
+  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
+                  dy.sizes() == x.sizes(),
+              "causal_conv_silu_bwd: dy must match x");
+}
+
 // Dv-split rule shared by every chunk launch: below ~1.5 workgroups/CU the
 // duplicated K-side work is cheaper than idle CUs.
 bool gdn_split_dv(int64_t n_wg) { return n_wg * 2 <= 384; }
@@ -1062,6 +1078,29 @@ void gdn_bwd_scan_launch(int64_t n_wg, int64_t S, const torch::Tensor& q,
   }
 }
 
+// dense entry points: (B, H, S, 64) bf16 rows + (B, H, S) gates
+void gdn_dense_checks(const char* who, const torch::Tensor& q,
+                      const torch::Tensor& k, const torch::Tensor& v,
+                      const torch::Tensor& beta,
+                      const torch::Tensor& decay_log) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16, who,
+              ": q must be a bf16 device tensor");
+  TORCH_CHECK(k.is_cuda() && k.scalar_type() == torch::kBFloat16, who,
+              ": k must be a bf16 device tensor");
+  TORCH_CHECK(v.is_cuda() && v.scalar_type() == torch::kBFloat16, who,
+              ": v / dout must be a bf16 device tensor");
+  TORCH_CHECK(q.dim() == 4 && q.size(-1) == 64, who,
+              " supports (B, H, S, 64)");
+  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(), who,
+              ": q, k, v / dout must share one (B, H, S, 64) shape");
+  TORCH_CHECK(beta.is_cuda() && decay_log.is_cuda(), who,
+              ": beta and decay_log must be device tensors");
+  TORCH_CHECK(beta.dim() == 3 && beta.size(0) == q.size(0) &&
+                  beta.size(1) == q.size(1) && beta.size(2) == q.size(2) &&
+                  decay_log.sizes() == beta.sizes(),
+              who, ": beta and decay_log must be (B, H, S)");
+}
+
 // (1, H, T, 64) bf16 rows + (1, H, T) gates of one packed row
 void gdn_varlen_checks(const torch::Tensor& q, const torch::Tensor& k,
                        const torch::Tensor& v, const torch::Tensor& beta,
@@ -1090,6 +1129,7 @@ torch::Tensor causal_conv_silu_fwd(torch::Tensor x, torch::Tensor w) {
 
 std::vector<torch::Tensor> causal_conv_silu_bwd(
     torch::Tensor x, torch::Tensor w, torch::Tensor dy) {
+  conv_bwd_checks(x, w, dy);
   return conv_silu_bwd_impl<false>(x, w, dy, nullptr, 0);
 }
 
@@ -1118,9 +1158,7 @@ std::vector<torch::Tensor> causal_conv_silu_varlen_bwd(
 std::vector<torch::Tensor> gdn_chunk_bwd_scan(
     torch::Tensor q, torch::Tensor k, torch::Tensor dout,
     torch::Tensor beta, torch::Tensor decay_log) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(dout.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(q.size(-1) == 64, "gdn_chunk_bwd_scan supports D = 64");
+  gdn_dense_checks("gdn_chunk_bwd_scan", q, k, dout, beta, decay_log);
   auto qc = q.contiguous();
   auto kc = k.contiguous();
   auto dc = dout.contiguous();
@@ -1217,9 +1255,7 @@ std::vector<torch::Tensor> gdn_chunk_fwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor beta, torch::Tensor decay_log, bool return_state,
     bool return_aux, bool skip_out) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(q.size(-1) == 64 && v.size(-1) == 64,
-              "gdn_chunk_fwd supports Dk = Dv = 64");
+  gdn_dense_checks("gdn_chunk_fwd", q, k, v, beta, decay_log);
   return gdn_chunk_fwd_impl<false>(
       q, k, v, beta, decay_log, return_state, return_aux, skip_out,
       {q.size(0), q.size(1)}, (q.size(2) + 63) / 64, nullptr, nullptr);

@@ -170,7 +170,14 @@ torch::Tensor silu_mul_fwd(torch::Tensor a, torch::Tensor b) {
 
 std::vector<torch::Tensor> silu_mul_bwd(
     torch::Tensor a, torch::Tensor b, torch::Tensor g) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 && a.is_contiguous());
+  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 && a.is_contiguous(),
+              "silu_mul_bwd: a must be a contiguous bf16 device tensor");
+  TORCH_CHECK(b.is_cuda() && b.sizes() == a.sizes() &&
+                  b.scalar_type() == torch::kBFloat16 && b.is_contiguous(),
+              "silu_mul_bwd: b must match a");
+  TORCH_CHECK(g.is_cuda() && g.sizes() == a.sizes() &&
+                  g.scalar_type() == torch::kBFloat16 && g.is_contiguous(),
+              "silu_mul_bwd: g must match a");
   auto da = torch::empty_like(a);
   auto db = torch::empty_like(b);
   const int64_t n = a.numel();
@@ -210,9 +217,15 @@ torch::Tensor silu_mul_packed_fwd(torch::Tensor x) {
 
 torch::Tensor silu_mul_packed_bwd(torch::Tensor x, torch::Tensor g) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.is_contiguous());
-  TORCH_CHECK(g.is_contiguous() && g.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(x.dim() == 2, "silu_mul_packed_bwd: x must be (T, 2I)");
   const int64_t rows = x.size(0);
   const int inter = (int)x.size(1) / 2;
+  TORCH_CHECK(x.size(1) % 2 == 0 && inter % 8 == 0,
+              "silu_mul_packed_bwd: packed silu_mul needs I % 8 == 0");
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous() &&
+                  g.scalar_type() == torch::kBFloat16 && g.dim() == 2 &&
+                  g.size(0) == rows && g.size(1) == inter,
+              "silu_mul_packed_bwd: g must be a contiguous bf16 (T, I)");
   auto dx = torch::empty_like(x);
   if (x.numel() == 0) return dx;
   constexpr int kBlock = 256;

@@ -369,36 +369,42 @@ void adamw_stochastic_bf16_(
 }
 
 
-void adamw_stochastic_bf16_multi_(
-    std::vector<torch::Tensor> params, std::vector<torch::Tensor> grads,
-    std::vector<torch::Tensor> exp_avgs, std::vector<torch::Tensor> exp_avg_sqs,
+namespace {
+
+// One launch over tensors [lo, hi) of the lists; the lookup tables of the
+// range must fit the 64 KiB of LDS the kernel stages them in.
+void adamw_multi_launch(
+    const std::vector<torch::Tensor>& params,
+    const std::vector<torch::Tensor>& grads,
+    const std::vector<torch::Tensor>& exp_avgs,
+    const std::vector<torch::Tensor>& exp_avg_sqs,
     double lr, double beta1, double beta2, double eps, double weight_decay,
-    std::vector<int64_t> steps, std::vector<int64_t> seeds) {
-  const int n = (int)params.size();
-  if (n == 0) return;
+    const std::vector<int64_t>& steps, const std::vector<int64_t>& seeds,
+    size_t lo, size_t hi) {
+  const int n = (int)(hi - lo);
   auto meta_cpu = torch::empty({(int64_t)n * 7 + 1}, torch::dtype(torch::kInt64));
   auto bc_cpu = torch::empty({(int64_t)n * 2}, torch::dtype(torch::kFloat32));
   int64_t* mp = meta_cpu.data_ptr<int64_t>();
   float* bp = bc_cpu.data_ptr<float>();
   int64_t slots = 0;
   for (int i = 0; i < n; ++i) {
-    TORCH_CHECK(params[i].is_cuda() && params[i].scalar_type() == torch::kBFloat16);
-    TORCH_CHECK(grads[i].is_contiguous() && params[i].is_contiguous());
-    const int64_t cnt = params[i].numel();
+    const size_t j = lo + i;
+    const int64_t cnt = params[j].numel();
     mp[i] = slots;                          // prefix
     mp[n + 1 + i] = cnt;                    // count
-    mp[2 * n + 1 + i] = (int64_t)params[i].data_ptr();
-    mp[3 * n + 1 + i] = (int64_t)grads[i].data_ptr();
-    mp[4 * n + 1 + i] = (int64_t)exp_avgs[i].data_ptr();
-    mp[5 * n + 1 + i] = (int64_t)exp_avg_sqs[i].data_ptr();
-    mp[6 * n + 1 + i] = seeds[i];
-    bp[i * 2] = 1.f - powf((float)beta1, (float)steps[i]);
-    bp[i * 2 + 1] = 1.f - powf((float)beta2, (float)steps[i]);
+    mp[2 * n + 1 + i] = (int64_t)params[j].data_ptr();
+    mp[3 * n + 1 + i] = (int64_t)grads[j].data_ptr();
+    mp[4 * n + 1 + i] = (int64_t)exp_avgs[j].data_ptr();
+    mp[5 * n + 1 + i] = (int64_t)exp_avg_sqs[j].data_ptr();
+    mp[6 * n + 1 + i] = seeds[j];
+    bp[i * 2] = 1.f - powf((float)beta1, (float)steps[j]);
+    bp[i * 2 + 1] = 1.f - powf((float)beta2, (float)steps[j]);
     slots += (cnt + 7) / 8;
   }
   mp[n] = slots;
-  auto meta = meta_cpu.to(params[0].device(), /*non_blocking=*/true);
-  auto bc = bc_cpu.to(params[0].device(), /*non_blocking=*/true);
+  if (slots == 0) return;  // only empty tensors in this range
+  auto meta = meta_cpu.to(params[lo].device(), /*non_blocking=*/true);
+  auto bc = bc_cpu.to(params[lo].device(), /*non_blocking=*/true);
   constexpr int kBlock = 256;
   const int grid = (int)std::min<int64_t>((slots + kBlock - 1) / kBlock, 16384);
   const size_t smem = (7 * (size_t)n + 1) * 8 + 2 * (size_t)n * 4;
@@ -408,4 +414,47 @@ void adamw_stochastic_bf16_multi_(
                      dim3(kBlock), smem, stream, meta.data_ptr<int64_t>(),
                      bc.data_ptr<float>(), n, slots, (float)lr, (float)beta1,
                      (float)beta2, (float)eps, (float)weight_decay);
+}
+
+}  // namespace
+
+void adamw_stochastic_bf16_multi_(
+    std::vector<torch::Tensor> params, std::vector<torch::Tensor> grads,
+    std::vector<torch::Tensor> exp_avgs, std::vector<torch::Tensor> exp_avg_sqs,
+    double lr, double beta1, double beta2, double eps, double weight_decay,
+    std::vector<int64_t> steps, std::vector<int64_t> seeds) {
+  const size_t n = params.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n &&
+                  exp_avg_sqs.size() == n && steps.size() == n &&
+                  seeds.size() == n,
+              "adamw multi: every list must have one entry per parameter");
+  if (n == 0) return;
+  const auto device = params[0].device();
+  for (size_t i = 0; i < n; ++i) {
+    const auto& p = params[i];
+    const auto& g = grads[i];
+    const auto& m = exp_avgs[i];
+    const auto& v = exp_avg_sqs[i];
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kBFloat16 &&
+                    p.is_contiguous(),
+                "adamw multi: param ", i, " must be a contiguous bf16 device tensor");
+    TORCH_CHECK(g.scalar_type() == torch::kBFloat16 && g.is_contiguous(),
+                "adamw multi: grad ", i, " must be contiguous bf16");
+    TORCH_CHECK(m.scalar_type() == torch::kFloat32 && m.is_contiguous() &&
+                    v.scalar_type() == torch::kFloat32 && v.is_contiguous(),
+                "adamw multi: moments ", i, " must be contiguous fp32");
+    TORCH_CHECK(p.device() == device && g.device() == device &&
+                    m.device() == device && v.device() == device,
+                "adamw multi: tensors of entry ", i, " must share the device of param 0");
+    const int64_t cnt = p.numel();
+    TORCH_CHECK(g.numel() == cnt && m.numel() == cnt && v.numel() == cnt,
+                "adamw multi: numel mismatch at entry ", i);
+  }
+  // 64 B of lookup tables per tensor (+8): split the list at the LDS limit
+  constexpr size_t kMaxTensors = (64 * 1024 - 8) / 64;
+  for (size_t lo = 0; lo < n; lo += kMaxTensors) {
+    adamw_multi_launch(params, grads, exp_avgs, exp_avg_sqs, lr, beta1, beta2,
+                       eps, weight_decay, steps, seeds, lo,
+                       std::min(n, lo + kMaxTensors));
+  }
 }

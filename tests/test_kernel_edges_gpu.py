@@ -31,6 +31,25 @@ Branch -> test:
   attention non-causal ragged bwd ...................... test_attn_noncausal_ragged
   attention dlse ....................................... test_attn_dlse, test_attn_varlen_dlse,
                                                          test_attn_lse_only_loss
+  gdn fwd DVT=32 / DVT=64, S < 64, tails, chunk carry,
+    planted solve; out, final_state, r, s0 ............. test_gdn_fwd_edges
+  gdn fwd return-list order per flag triple ............ test_gdn_fwd_return_order
+  gdn bwd scan kernels DVT=32 / DVT=64 through the op .. test_gdn_bwd_edges[(2,3,128)/(1,193,128)]
+  gdn bwd pad != 0 torch-scan branch on the GPU ........ test_gdn_bwd_edges[(2,3,130)]
+  gdn varlen fwd + bwd, per-document reference ......... test_gdn_varlen_bwd
+  gdn_chunk_bwd_scan tail rows (direct call, S = 100) .. test_gdn_bwd_scan_tail
+  conv K 1..4, S < K, grid loop ........................ test_conv_silu_edges
+  SR copy seed contract, tail salt, both loops twice ... test_sr_copy_bitwise
+  adamw single kernel, tails, second grid iteration .... test_adamw_edges, test_adamw_sr_mean
+  adamw multi per-tensor step/seed, empty tensor ....... test_adamw_multi_steps_and_seeds
+  adamw multi pipelined loop, walk across tensors ...... test_adamw_multi_pipelined_loop
+  adamw multi split at the LDS limit ................... test_adamw_multi_many_tensors
+  StochasticAdamW seed formula, grad None, fp32 grad ... test_stochastic_adamw_class
+  add_bf16_into_f32_ tail and grid loop ................ test_add_bf16_into_f32
+  silu_mul tails, grid loop, extreme gates ............. test_silu_mul_edges
+  silu_mul_packed grid loop, last columns, I % 8 ....... test_silu_mul_packed_edges,
+                                                         test_silu_mul_packed_needs_multiple_of_8
+  gdn / conv / silu / adamw-multi argument checks ...... test_*_reject_bad_arguments
 """
 
 import pytest
@@ -46,8 +65,14 @@ from tests.test_kernel_edges import (
     VARLEN_CASES,
     _permute_run,
     _unpermute_run,
+    adamw_single_run,
     attn_run,
     attn_varlen_run,
+    check_stochastic_adamw_class,
+    conv_run,
+    gdn_op_run,
+    silu_packed_run,
+    silu_run,
 )
 
 pytestmark = pytest.mark.gpu
@@ -445,3 +470,319 @@ def test_attn_lse_only_loss():
     kr.assert_close(q.grad, q64.grad, kr.TOL_ATTN_DQ, "dq")
     kr.assert_close(k.grad, k64.grad, kr.TOL_ATTN_GRAD, "dk")
     assert float(v.grad.abs().max()) == 0.0
+
+
+# ---- GatedDeltaNet -------------------------------------------------------------
+
+
+def _gdn_dev(case, names=("q", "k", "v", "beta", "g")):
+    return [case[n].to(DEV) for n in names]
+
+
+def _gdn_fwd_gpu(case):
+    out, fs, r, s0 = _ext().gdn_chunk_fwd(*_gdn_dev(case), True, True, False)
+    assert out.dtype == torch.bfloat16 and fs.dtype == r.dtype == s0.dtype == torch.float32
+    return dict(out=out, fs=fs, r=r, s0=s0)
+
+
+@pytest.mark.parametrize("shape", kr.GDN_FWD_SHAPES, ids=str)
+def test_gdn_fwd_edges(shape):
+    """Both Dv instantiations (B*H = 6 -> DVT 32, B*H = 193 -> DVT 64),
+    S = 1, S < 64, S = 64, one tail row, a tail after two chunks, three full
+    chunks; runs of a repeated key (a solve that is far from the identity),
+    state wipes, beta = 0 rows and a poisoned row behind every tail. All four
+    outputs against the fp64 recurrence."""
+    kr.check_gdn_fwd(_gdn_fwd_gpu, *shape)
+
+
+def test_gdn_fwd_return_order():
+    """[out unless skip_out] + [final_state if return_state] + [r, s0 if
+    return_aux], each equal to what the full call returns."""
+    case = kr.gdn_case(2, 3, 65)
+    args = _gdn_dev(case)
+    full = _gdn_fwd_gpu(case)
+    for return_state, return_aux, skip_out in kr.GDN_FLAG_TRIPLES:
+        got = _ext().gdn_chunk_fwd(*args, return_state, return_aux, skip_out)
+        want = ([] if skip_out else ["out"]) + (["fs"] if return_state else []) + (
+            ["r", "s0"] if return_aux else []
+        )
+        assert len(got) == len(want), (return_state, return_aux, skip_out)
+        for name, t in zip(want, got):
+            kr.assert_same_bits(t, full[name], f"{name} of {(return_state, return_aux, skip_out)}")
+
+
+@pytest.mark.parametrize("shape", kr.GDN_BWD_SHAPES, ids=str)
+def test_gdn_bwd_edges(shape):
+    """chunk_gated_delta_rule forward + backward against autograd on the
+    fp64 recurrence: the scan kernels at both Dv widths (S = 128) and the
+    torch-scan branch a tail selects on the GPU (S = 130)."""
+    kr.check_gdn_bwd(gdn_op_run(DEV), *shape)
+
+
+def test_gdn_varlen_bwd():
+    """Packed documents of 1, 64, 63, 65, 0, 130 and 7 rows through the
+    varlen kernels; each document against the recurrence on it alone."""
+    kr.check_gdn_varlen_bwd(gdn_op_run(DEV), kr.GDN_VARLEN_LENS, 3)
+
+
+def test_gdn_bwd_scan_tail():
+    """gdn_chunk_bwd_scan at S = 100: the op never sends it a tail, a direct
+    call does. drhs = dv / beta and dS0 = the boundary state's gradient."""
+
+    def run(case):
+        drhs, ds0 = _ext().gdn_chunk_bwd_scan(*_gdn_dev(case, ("q", "k", "dout", "beta", "g")))
+        return drhs, ds0
+
+    kr.check_gdn_bwd_scan(run, 2, 3, 100)
+
+
+@pytest.mark.parametrize("shape", kr.CONV_SHAPES, ids=str)
+def test_conv_silu_edges(shape):
+    """K = 1..4 with S below, at and above K, and the grid-stride loop
+    ((2, 1030, 1024, 4) is 2 109 440 elements for 8192 x 256 threads)."""
+    kr.check_conv(conv_run(DEV), *shape)
+
+
+def test_gdn_entry_points_reject_bad_arguments():
+    """The dense chunk entry points and the conv backward refuse what the
+    kernels would reinterpret. Every bad tensor is at least as large as the
+    good one."""
+    ext = _ext()
+    case = kr.gdn_case(1, 2, 70)
+    q, k, v, beta, g = _gdn_dev(case)
+    dout = case["dout"].to(DEV)
+    longer = torch.cat([k, k[:, :, :1]], 2)
+    beta_longer = torch.cat([beta, beta[:, :, :1]], 2)
+    for name, fn, third in (("gdn_chunk_fwd", lambda *a: ext.gdn_chunk_fwd(*a, False, False, False), v),
+                            ("gdn_chunk_bwd_scan", ext.gdn_chunk_bwd_scan, dout)):
+        bad_calls = [
+            lambda: fn(q, k.float(), third, beta, g),
+            lambda: fn(q, k, third.float(), beta, g),
+            lambda: fn(q.float(), k, third, beta, g),
+            lambda: fn(q, longer, third, beta, g),
+            lambda: fn(q, k, longer, beta, g),
+            lambda: fn(q, case["k"], third, beta, g),
+            lambda: fn(q, k, third.cpu(), beta, g),
+            lambda: fn(q, k, third, case["beta"], g),
+            lambda: fn(q, k, third, beta, case["g"]),
+            lambda: fn(q, k, third, beta_longer, g),
+            lambda: fn(q, k, third, beta, beta_longer),
+            lambda: fn(q, k, third, beta.unsqueeze(-1), g),
+            lambda: fn(q[0], k[0], third[0], beta[0], g[0]),
+        ]
+        for i, call in enumerate(bad_calls):
+            with pytest.raises(RuntimeError, match=name):
+                call()
+                pytest.fail(f"{name}: bad call {i} was accepted")
+    x, w, dy = (t.to(DEV) for t in kr.conv_case(2, 37, 48, 4))
+    bad_calls = [
+        lambda: ext.causal_conv_silu_bwd(x.float(), w, dy),
+        lambda: ext.causal_conv_silu_bwd(x, w.float(), dy),
+        lambda: ext.causal_conv_silu_bwd(x, w, dy.float()),
+        lambda: ext.causal_conv_silu_bwd(x, w, dy.cpu()),
+        lambda: ext.causal_conv_silu_bwd(x, w.cpu(), dy),
+        lambda: ext.causal_conv_silu_bwd(x, w, torch.cat([dy, dy], 1)),
+        lambda: ext.causal_conv_silu_bwd(x, torch.cat([w, w], 0), dy),
+        lambda: ext.causal_conv_silu_bwd(x, torch.cat([w, w], 1), dy),
+        lambda: ext.causal_conv_silu_bwd(x[0], w, dy[0]),
+    ]
+    for i, call in enumerate(bad_calls):
+        with pytest.raises(RuntimeError, match="causal_conv_silu_bwd"):
+            call()
+            pytest.fail(f"conv: bad call {i} was accepted")
+
+
+# ---- Stochastic rounding and AdamW ------------------------------------------------
+
+
+def _sr_copy_gpu(src, seed):
+    dst = torch.empty(src.shape, dtype=torch.bfloat16, device=DEV)
+    _ext().copy_fp32_to_bf16_stochastic_(dst, src.to(DEV), seed)
+    return dst
+
+
+@pytest.mark.parametrize("seed", [7, 2 ** 62 + 12345])
+@pytest.mark.parametrize("n", kr.SR_COPY_SIZES)
+def test_sr_copy_bitwise(n, seed):
+    """The seed contract, bit for bit: vector body, scalar tail (n % 4), a
+    second trip through both loops (n = 2 097 303), +-0, +-inf, NaN, grid
+    values and the five low-half fractions on both signs. The oracle's
+    statistics are asserted in the CPU suite and hold here by equality."""
+    kr.check_sr_copy(_sr_copy_gpu, n, seed)
+
+
+@pytest.mark.parametrize("hyper", kr.ADAMW_HYPER, ids=lambda h: f"lr{h['lr']}")
+@pytest.mark.parametrize("n", kr.ADAMW_SIZES)
+def test_adamw_edges(n, hyper):
+    """Every element within one bf16 ulp of the fp64 step, no bias over the
+    tensor, moments at fp32 accuracy; n = 2 097 303 takes both loops twice."""
+    kr.check_adamw(adamw_single_run(DEV), n, hyper)
+
+
+def test_adamw_sr_mean():
+    kr.check_adamw_sr_mean(adamw_single_run(DEV))
+
+
+ADAMW_ARGS = (1e-3, 0.9, 0.95, 1e-8, 0.01)
+
+
+def _adamw_multi_vs_single(sizes, steps, seeds):
+    """The documented contract: one multi-tensor launch equals per-tensor
+    single-kernel calls, bit for bit, in p, exp_avg and exp_avg_sq."""
+    ext = _ext()
+    ps, gs, ms, vs = kr.adamw_multi_case(sizes)
+    gs = [t.to(DEV) for t in gs]
+    one = [[t.to(DEV) for t in lst] for lst in (ps, ms, vs)]
+    many = [[t.to(DEV) for t in lst] for lst in (ps, ms, vs)]
+    for i in range(len(sizes)):
+        ext.adamw_stochastic_bf16_(
+            one[0][i], gs[i], one[1][i], one[2][i], *ADAMW_ARGS, steps[i], seeds[i]
+        )
+    ext.adamw_stochastic_bf16_multi_(many[0], gs, many[1], many[2], *ADAMW_ARGS, steps, seeds)
+    changed = 0
+    for i in range(len(sizes)):
+        for a, b, view, what in zip(one, many, (torch.int16, torch.int32, torch.int32),
+                                    ("p", "exp_avg", "exp_avg_sq")):
+            same = torch.equal(a[i].view(view), b[i].view(view))
+            assert same, f"{what} of tensor {i} ({sizes[i]} elements) differs"
+        changed += int((one[0][i].cpu() != ps[i]).sum())
+    assert changed > 0.3 * sum(sizes)   # the step did something
+
+
+def test_adamw_multi_steps_and_seeds():
+    """A different step (bias correction) and seed per tensor, an empty
+    tensor in the middle, a partial slot that still holds a 4-vector."""
+    small = kr.ADAMW_MULTI_SMALL
+    _adamw_multi_vs_single(small["sizes"], small["steps"], small["seeds"])
+
+
+def test_adamw_multi_pipelined_loop():
+    """More slots than threads: the software-pipelined loop runs, and a
+    thread's second slot lies several tensors after its first."""
+    sizes = kr.adamw_multi_big_sizes()
+    steps = [1 + i % 7 for i in range(len(sizes))]
+    seeds = [1000 + 37 * i for i in range(len(sizes))]
+    _adamw_multi_vs_single(sizes, steps, seeds)
+
+
+def test_adamw_multi_many_tensors():
+    """1 200 tensors need more lookup-table space than one launch has LDS:
+    the wrapper splits the list."""
+    n = 1200
+    _adamw_multi_vs_single([8] * n, [1 + i % 5 for i in range(n)], [1 + 7919 * i for i in range(n)])
+
+
+def test_stochastic_adamw_class():
+    check_stochastic_adamw_class(DEV)
+
+
+def test_adamw_multi_rejects_bad_arguments():
+    ext = _ext()
+    sizes = [64, 24]
+    ps, gs, ms, vs = ([t.to(DEV) for t in lst] for lst in kr.adamw_multi_case(sizes))
+    steps, seeds = [1, 2], [3, 4]
+    extra = torch.zeros(64, device=DEV)
+
+    def call(ps=ps, gs=gs, ms=ms, vs=vs, steps=steps, seeds=seeds):
+        return lambda: ext.adamw_stochastic_bf16_multi_(ps, gs, ms, vs, *ADAMW_ARGS, steps, seeds)
+
+    def swap(lst, t):
+        return [t] + lst[1:]
+
+    strided = torch.zeros(64, 2, device=DEV)
+    bad_calls = [
+        call(gs=gs + [extra.bfloat16()]),
+        call(ms=ms + [extra]),
+        call(vs=vs + [extra]),
+        call(steps=steps + [1]),
+        call(seeds=seeds + [1]),
+        call(ps=swap(ps, extra)),                               # fp32 parameter
+        call(gs=swap(gs, extra)),                               # fp32 grad
+        call(ms=swap(ms, extra.double())),
+        call(vs=swap(vs, extra.double())),
+        call(gs=swap(gs, strided.bfloat16()[:, 0])),
+        call(ms=swap(ms, strided[:, 0])),
+        call(ps=swap(ps, strided.bfloat16()[:, 0])),
+        call(gs=swap(gs, torch.zeros(65, dtype=torch.bfloat16, device=DEV))),
+        call(vs=swap(vs, torch.zeros(65, device=DEV))),
+        call(gs=swap(gs, gs[0].cpu())),
+        call(ms=swap(ms, ms[0].cpu())),
+    ]
+    for i, bad in enumerate(bad_calls):
+        with pytest.raises(RuntimeError, match="adamw multi"):
+            bad()
+            pytest.fail(f"bad call {i} was accepted")
+
+
+@pytest.mark.parametrize("n", kr.ADD_BF16_SIZES)
+def test_add_bf16_into_f32(n):
+    """One IEEE add per element: the 8-wide body, the scalar tail and, at
+    33 554 475 elements, a second grid-stride iteration."""
+
+    def run(acc, x):
+        acc = acc.to(DEV)
+        _ext().add_bf16_into_f32_(acc, x.to(DEV))
+        return acc
+
+    kr.check_add_bf16_into_f32(run, n)
+
+
+# ---- SwiGLU ------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("n", kr.SILU_SIZES)
+def test_silu_mul_edges(n):
+    """n % 8 tails, more than 2048 x 256 vectors (a second grid-stride
+    iteration in both loops), gates where exp2 overflows or underflows and
+    where silu' changes sign."""
+    kr.check_silu(silu_run(DEV), n)
+
+
+@pytest.mark.parametrize("shape", kr.SILU_PACKED_SHAPES, ids=str)
+def test_silu_mul_packed_edges(shape):
+    """One vector per row, I not a power of two, and 528 900 vectors (past
+    the grid); the largest values in the last column of each half."""
+    kr.check_silu_packed(silu_packed_run(DEV), *shape)
+
+
+def test_silu_mul_packed_needs_multiple_of_8():
+    ext = _ext()
+    x = torch.zeros(4, 2 * 12, dtype=torch.bfloat16, device=DEV)
+    g = torch.zeros(4, 12, dtype=torch.bfloat16, device=DEV)
+    with pytest.raises(RuntimeError, match="I % 8"):
+        ext.silu_mul_packed_fwd(x)
+    with pytest.raises(RuntimeError, match="I % 8"):
+        ext.silu_mul_packed_bwd(x, g)
+
+
+def test_silu_entry_points_reject_bad_arguments():
+    ext = _ext()
+    a, b, g = (t.to(DEV) for t in kr.silu_case(64))
+    wide = torch.zeros(64, 2, dtype=torch.bfloat16, device=DEV)
+    bad_calls = [
+        lambda: ext.silu_mul_bwd(a, b.float(), g),
+        lambda: ext.silu_mul_bwd(a, b, g.float()),
+        lambda: ext.silu_mul_bwd(a, b.cpu(), g),
+        lambda: ext.silu_mul_bwd(a, b, g.cpu()),
+        lambda: ext.silu_mul_bwd(a, wide[:, 0], g),
+        lambda: ext.silu_mul_bwd(a, b, wide[:, 0]),
+        lambda: ext.silu_mul_bwd(a, torch.cat([b, b]), g),
+        lambda: ext.silu_mul_bwd(a, b, torch.cat([g, g])),
+    ]
+    for i, call in enumerate(bad_calls):
+        with pytest.raises(RuntimeError, match="silu_mul_bwd"):
+            call()
+            pytest.fail(f"bad call {i} was accepted")
+    x, gp = (t.to(DEV) for t in kr.silu_packed_case(3, 72))
+    bad_calls = [
+        lambda: ext.silu_mul_packed_bwd(x, gp.float()),
+        lambda: ext.silu_mul_packed_bwd(x, gp.cpu()),
+        lambda: ext.silu_mul_packed_bwd(x, torch.cat([gp, gp], 0)),
+        lambda: ext.silu_mul_packed_bwd(x, torch.cat([gp, gp], 1)),
+        lambda: ext.silu_mul_packed_bwd(x, torch.cat([gp, gp], 1)[:, :72]),
+        lambda: ext.silu_mul_packed_bwd(x, gp.reshape(-1)),
+    ]
+    for i, call in enumerate(bad_calls):
+        with pytest.raises(RuntimeError, match="silu_mul_packed_bwd"):
+            call()
+            pytest.fail(f"packed: bad call {i} was accepted")
