@@ -16,8 +16,14 @@
 //     transposed images derived LDS-to-LDS); dK/dV accumulate in registers,
 //     dQ via fp32 global atomics; delta = rowsum(dO*O) precomputed.
 //
-// Layouts: q (B,Sq,Hq,D), k/v (B,Skv,Hkv,D), out (B,Sq,Hq,D), lse (B,Hq,Sq).
-// D (head_dim) templated in {32, 64, 96, 128}; host pads other sizes.
+// Layouts: q (B,Sq,Hq,Dqk), k (B,Skv,Hkv,Dqk), v (B,Skv,Hkv,Dv),
+// out (B,Sq,Hq,Dv), lse (B,Hq,Sq). The kernels are templated on the pair
+// <DQK, DV>: Q, K, S = Q K^T, dQ and dK run over DQK; V, O, dO, dP = dO V^T,
+// dV and delta over DV. Instantiated: DQK = DV in {32, 64, 96, 128} and the
+// one wide pair <192, 128> (MLA: qk 192 / v 128), whose forward takes 64 q
+// rows per workgroup (one m-tile per wave) to stay inside 256 VGPRs and whose
+// backward stages 32 q rows per tile instead of 64 to fit the LDS. The host
+// pads other sizes up to the next pair; qk > 192 or v > 128 is an error.
 #include "common.h"
 #include "mfma.h"
 
@@ -29,8 +35,10 @@
 namespace d9d {
 
 constexpr int kFwdQ = 128;   // forward: q rows per workgroup (4 waves x 32)
+constexpr int kFwdQWide = 64;  // ... and for the wide pair <192, 128> (4 x 16)
 constexpr int kFwdKv = 64;   // forward: kv rows per staged K/V tile
-constexpr int kBwdQ = 64;    // backward: q rows per staged Q/dO tile
+constexpr int kBwdQ = 64;    // backward: q rows per staged Q/dO tile (DQK <= 128)
+constexpr int kBwdQWide = 32;  // ... and for the wide pair <192, 128>
 constexpr int kBwdKv = 128;  // backward: kv rows per workgroup (8 waves x 16)
 constexpr int kBwdThreads = 512;
 constexpr float kLog2e = 1.44269504088896340736f;
@@ -39,10 +47,11 @@ constexpr float kLog2e = 1.44269504088896340736f;
 // 16-byte units and must stay inside the LDS row: a mask of m bits needs rows
 // that are a multiple of 16 << m bytes. Row-major [rows][D] tiles (D*2-byte
 // rows) use swz_rm_mask<D>() -- D = 96 has 192-byte rows, a multiple of 64
-// only, so it takes the 2-bit mask; transposed [D][ROWS] tiles use mask 7.
+// only, so it takes the 2-bit mask, D = 192 (384-byte rows) the 3-bit one;
+// transposed [D][ROWS] tiles use mask 7, or 3 where ROWS = 32 (64-byte rows).
 template <int D>
 constexpr int swz_rm_mask() {
-  constexpr int mask = D == 128 ? 15 : (D == 64 ? 7 : 3);
+  constexpr int mask = D == 128 ? 15 : ((D == 64 || D == 192) ? 7 : 3);
   static_assert((D * 2) % (16 * (mask + 1)) == 0, "swizzle leaves its LDS row");
   return mask;
 }
@@ -58,22 +67,24 @@ D9D_DEVICE Byte* swz_rm_at(Byte* tile, int row, int col) {
 // Address of element (d, r) in a swizzled transposed [D][ROWS] tile.
 template <int ROWS, typename Byte>
 D9D_DEVICE Byte* swz_t_at(Byte* tile, int d, int r) {
-  static_assert((ROWS * 2) % (16 << 3) == 0, "swizzle leaves its LDS row");
-  return tile + d * (ROWS * 2) + ((r * 2) ^ ((d & 7) << 4));
+  constexpr int mask = ROWS * 2 >= 128 ? 7 : 3;
+  static_assert((ROWS * 2) % (16 * (mask + 1)) == 0, "swizzle leaves its LDS row");
+  return tile + d * (ROWS * 2) + ((r * 2) ^ ((d & mask) << 4));
 }
 
-// Transpose a swizzled row-major [64][D] LDS image into a swizzled [D][64]
-// LDS image using 4B LDS reads + 8B LDS writes.
-template <int D, int BLOCK = 256>
+// Transpose a swizzled row-major [ROWS][D] LDS image into a swizzled
+// [D][ROWS] LDS image using 4B LDS reads + 8B LDS writes.
+template <int D, int ROWS, int BLOCK = 256>
 D9D_DEVICE void transpose_lds_tile(bf16_t* dst, const bf16_t* src_rm, int tid) {
   // Work mapping: consecutive threads take consecutive ROW-quads of the
-  // same d-pair, so the two b64 writes of a 16-thread group land on one
-  // [d][64] row contiguously (128 B span, conflict-free). The b32 source
-  // reads pay a 4-way conflict instead of the old mapping's 8-way b64
-  // write conflict (rows 256 B apart XOR-spread only 4 ways per group).
-  for (int idx = tid; idx < (64 / 4) * (D / 2); idx += BLOCK) {
-    const int d0 = (idx / 16) * 2;
-    const int rb = (idx % 16) * 4;
+  // same d-pair, so the two b64 writes of a ROWS/4-thread group land on one
+  // [d][ROWS] row contiguously (128 B span at 64 rows, conflict-free). The
+  // b32 source reads pay a 4-way conflict instead of the old mapping's 8-way
+  // b64 write conflict (rows 256 B apart XOR-spread only 4 ways per group).
+  constexpr int kQuads = ROWS / 4;
+  for (int idx = tid; idx < kQuads * (D / 2); idx += BLOCK) {
+    const int d0 = (idx / kQuads) * 2;
+    const int rb = (idx % kQuads) * 4;
     bf16x4_bits c0, c1;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -83,9 +94,9 @@ D9D_DEVICE void transpose_lds_tile(bf16_t* dst, const bf16_t* src_rm, int tid) {
       c1.s[i] = (ushort)(pair >> 16);
     }
     *reinterpret_cast<uint64_t*>(
-        swz_t_at<64>(reinterpret_cast<char*>(dst), d0, rb)) = c0.u;
+        swz_t_at<ROWS>(reinterpret_cast<char*>(dst), d0, rb)) = c0.u;
     *reinterpret_cast<uint64_t*>(
-        swz_t_at<64>(reinterpret_cast<char*>(dst), d0 + 1, rb)) = c1.u;
+        swz_t_at<ROWS>(reinterpret_cast<char*>(dst), d0 + 1, rb)) = c1.u;
   }
 }
 
@@ -226,28 +237,41 @@ D9D_DEVICE bool causal_window_masked(bool masked, int q_pos, int kv_pos,
 // Forward
 // ---------------------------------------------------------------------------
 
-template <int D>
+// FQ: q rows per workgroup. Two workgroups per CU (a 256-VGPR budget); up to
+// DQK = 128 the kernel just fits with kFwdQ rows (two m-tiles per wave). The
+// wide pair holds 16 more q_frag and 8 more k_reg registers, so it takes
+// kFwdQWide rows (one m-tile per wave) instead of spilling.
+template <int DQK, int DV, int FQ>
 __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
-    const bf16_t* __restrict__ q,   // (B,Sq,Hq,D)
-    const bf16_t* __restrict__ k,   // (B,Skv,Hkv,D)
-    const bf16_t* __restrict__ v,   // (B,Skv,Hkv,D)
-    bf16_t* __restrict__ out,       // (B,Sq,Hq,D)
+    const bf16_t* __restrict__ q,   // (B,Sq,Hq,DQK)
+    const bf16_t* __restrict__ k,   // (B,Skv,Hkv,DQK)
+    const bf16_t* __restrict__ v,   // (B,Skv,Hkv,DV)
+    bf16_t* __restrict__ out,       // (B,Sq,Hq,DV); DQK > 128: (2,B,Sq,Hq,DV)
     float* __restrict__ lse,        // (B,Hq,Sq)
     const float* __restrict__ sinks,  // (Hq,) raw sink logits, or nullptr
     const int* __restrict__ cu_q,     // (nseq+1,) packed-seq bounds, or nullptr
     const int* __restrict__ cu_k,
-    const int* __restrict__ qtile_pref,  // (nseq+1,) prefix of ceil(len_q/kFwdQ)
+    const int* __restrict__ qtile_pref,  // (nseq+1,) prefix of ceil(len_q/FQ)
     int nseq,
     int B, int Sq, int Skv, int Hq, int Hkv,
     float scale, int causal, int window_left, int q_offset) {
-  constexpr int kNT = D / 16;   // n-tiles over head dim
-  constexpr int kKS = D / 32;   // k-steps over head dim
+  static_assert(DV <= DQK, "the O staging reuses the K tile");
+  static_assert(FQ == 128 || FQ == 64, "q rows per workgroup");
+  constexpr int kM = FQ / 64;     // 16-row q m-tiles per wave
+  constexpr int kWaveQ = FQ / 4;  // q rows per wave
+  // The wide pair writes O's bf16 rounding residual as a second plane behind
+  // `out`, (2,B,Sq,Hq,DV): with it delta = rowsum(dO * O) is as exact as with
+  // an fp32 O. From the rounded O alone delta's error reaches dS un-averaged
+  // when the softmax is near one-hot (dq, dk off by 1e-1 at scale 0.5).
+  constexpr bool kOutLo = DQK > 128;
+  constexpr int kNT = DV / 16;   // n-tiles over the v head dim
+  constexpr int kKS = DQK / 32;  // k-steps over the qk head dim
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // [kFwdKv][D] swizzled, row p = kv row pv_pos(p); fwd_smem_bytes() is this
-  // carve-up
+  // [kFwdKv][DQK] swizzled, row p = kv row pv_pos(p); fwd_smem_bytes() is
+  // this carve-up
   bf16_t* k_lds = reinterpret_cast<bf16_t*>(smem);
-  bf16_t* vt_lds = k_lds + kFwdKv * D;               // [D][kFwdKv] transposed
+  bf16_t* vt_lds = k_lds + kFwdKv * DQK;             // [DV][kFwdKv] transposed
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -256,17 +280,22 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
   const bool upper = lane >= 32;
 
   // one (b, h)'s q-tiles share its KV stream (XCD grouping)
-  const TileLoc loc = locate_tile<kFwdQ, false>(
+  const TileLoc loc = locate_tile<FQ, false>(
       cu_q, cu_k, qtile_pref, nseq, Sq, Skv, Hq, q_offset);
   if (!loc.valid) return;
   const int b = loc.b, h = loc.h, q_tile = loc.tile, causal_off = loc.causal_off;
   const int q_lo = loc.q_lo, Sq_loc = loc.Sq_loc, kv_lo = loc.kv_lo, Skv_loc = loc.Skv_loc;
   const int hkv = h / (Hq / Hkv);
 
-  const int64_t q_base = ((int64_t)b * Sq * Hq + h) * D;
-  const int64_t kv_base = ((int64_t)b * Skv * Hkv + hkv) * D;
-  const int64_t q_row_stride = (int64_t)Hq * D;
-  const int64_t kv_row_stride = (int64_t)Hkv * D;
+  const int64_t q_base = ((int64_t)b * Sq * Hq + h) * DQK;
+  const int64_t kv_base = ((int64_t)b * Skv * Hkv + hkv) * DQK;
+  const int64_t q_row_stride = (int64_t)Hq * DQK;
+  const int64_t kv_row_stride = (int64_t)Hkv * DQK;
+  // the same for the DV-wide tensors (v, out); one value where DQK == DV
+  const int64_t o_base = DQK == DV ? q_base : ((int64_t)b * Sq * Hq + h) * DV;
+  const int64_t v_base = DQK == DV ? kv_base : ((int64_t)b * Skv * Hkv + hkv) * DV;
+  const int64_t o_row_stride = DQK == DV ? q_row_stride : (int64_t)Hq * DV;
+  const int64_t v_row_stride = DQK == DV ? kv_row_stride : (int64_t)Hkv * DV;
 
   // ---- load this wave's 32 q rows (2 sub-tiles) into fragments -------------
   // The kernel computes the TRANSPOSED products S^T = K Q^T and
@@ -274,10 +303,10 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
   // every value a lane holds belongs to ONE q row (lane & 15). The row
   // statistics are then per lane, and the S^T registers are already a legal
   // B operand for PV (see pv_pos): P never leaves the registers.
-  bf16x8 q_frag[2][kKS];
+  bf16x8 q_frag[kM][kKS];
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const int q_row_local = q_tile * kFwdQ + wave * 32 + m * 16 + lrow;
+  for (int m = 0; m < kM; ++m) {
+    const int q_row_local = q_tile * FQ + wave * kWaveQ + m * 16 + lrow;
     const int safe_row = q_lo + min(q_row_local, Sq_loc - 1);
     const bf16_t* qp = q + q_base + (int64_t)safe_row * q_row_stride;
 #pragma unroll
@@ -293,20 +322,20 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
   // l is kept as partial sums per kv column class (see the loop), merged at
   // the epilogue: seed the sink's column on class 0 only
   const float l_init = (sinks && lgrp == 0) ? 1.f : 0.f;
-  float m_run[2], l_run[2][4];
+  float m_run[kM], l_run[kM][4];
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
+  for (int m = 0; m < kM; ++m) {
     m_run[m] = m_init;
 #pragma unroll
     for (int r = 0; r < 4; ++r) l_run[m][r] = r == 0 ? l_init : 0.f;
   }
-  f32x4 o_acc[2][kNT];  // O^T: lane holds O[q = lrow][d = nt*16 + lgrp*4 + r]
+  f32x4 o_acc[kM][kNT];  // O^T: lane holds O[q = lrow][d = nt*16 + lgrp*4 + r]
 #pragma unroll
-  for (int m = 0; m < 2; ++m)
+  for (int m = 0; m < kM; ++m)
 #pragma unroll
     for (int nt = 0; nt < kNT; ++nt) o_acc[m][nt] = {0.f, 0.f, 0.f, 0.f};
 
-  const int q_tile_last_row = min(q_tile * kFwdQ + kFwdQ - 1, Sq_loc - 1);
+  const int q_tile_last_row = min(q_tile * FQ + FQ - 1, Sq_loc - 1);
   int kv_end = Skv_loc;
   if (causal) kv_end = min(Skv_loc, q_tile_last_row + causal_off + 1);
   const int num_kv_tiles = (kv_end + kFwdKv - 1) / kFwdKv;
@@ -315,8 +344,10 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
   // T14 split staging: next tile's K rows and V (4x2 transpose blocks) are
   // loaded into registers while the current tile's MFMAs run; LDS writes and
   // their vmcnt waits land after the compute barrier.
-  constexpr int kKIters = (kFwdKv * D) / (256 * 8);
-  constexpr int kVIters = (kFwdKv / 4) * (D / 2) / 256;
+  constexpr int kKIters = (kFwdKv * DQK) / (256 * 8);
+  constexpr int kVIters = (kFwdKv / 4) * (DV / 2) / 256;
+  static_assert(kKIters * 256 * 8 == kFwdKv * DQK &&
+                kVIters * 256 == (kFwdKv / 4) * (DV / 2), "staging covers the tiles");
   bf16x8 k_reg[kKIters];
   bf16x4_bits v_c0[kVIters], v_c1[kVIters];
 
@@ -325,16 +356,23 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
 #pragma unroll
     for (int it = 0; it < kKIters; ++it) {
       const int idx = (threadIdx.x + it * 256) * 8;
-      const int row = idx / D;
-      const int col = idx % D;
+      const int row = idx / DQK;
+      const int col = idx % DQK;
       const int g_row = kv_lo + min(kv0 + pv_pos(row), Skv_loc - 1);
       k_reg[it] = *reinterpret_cast<const bf16x8*>(
           k + kv_base + (int64_t)g_row * kv_row_stride + col);
     }
 #pragma unroll
     for (int it = 0; it < kVIters; ++it) {
-      load_transposed_block<D>(v_c0[it], v_c1[it], v + kv_base, kv_row_stride,
-                               kv_lo, kv0, Skv_loc - 1, threadIdx.x + it * 256);
+      // (v_base is kv_base where DQK == DV, but as one more captured variable
+      // it changes how the D = 32 prologue is vectorized and scheduled)
+      if constexpr (DQK == DV) {
+        load_transposed_block<DV>(v_c0[it], v_c1[it], v + kv_base, kv_row_stride,
+                                  kv_lo, kv0, Skv_loc - 1, threadIdx.x + it * 256);
+      } else {
+        load_transposed_block<DV>(v_c0[it], v_c1[it], v + v_base, v_row_stride,
+                                  kv_lo, kv0, Skv_loc - 1, threadIdx.x + it * 256);
+      }
     }
   };
 
@@ -343,13 +381,13 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
     for (int it = 0; it < kKIters; ++it) {
       const int idx = (threadIdx.x + it * 256) * 8;
       *reinterpret_cast<bf16x8*>(
-          swz_rm_at<D>(reinterpret_cast<char*>(k_lds), idx / D, idx % D)) =
+          swz_rm_at<DQK>(reinterpret_cast<char*>(k_lds), idx / DQK, idx % DQK)) =
           k_reg[it];
     }
 #pragma unroll
     for (int it = 0; it < kVIters; ++it) {
-      store_transposed_block<D, kFwdKv>(vt_lds, v_c0[it], v_c1[it],
-                                        threadIdx.x + it * 256);
+      store_transposed_block<DV, kFwdKv>(vt_lds, v_c0[it], v_c1[it],
+                                         threadIdx.x + it * 256);
     }
   };
 
@@ -364,9 +402,9 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
     // ---- S^T = K Q^T for both q sub-tiles; each K fragment is read once ----
     // lane holds S[q = lrow][kv = kv0 + pv_pos(nt*16 + lgrp*4 + r)] in
     // st[m][nt][r]
-    f32x4 st[2][4];
+    f32x4 st[kM][4];
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < kM; ++m)
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) st[m][nt] = {0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_s_setprio(1);
@@ -377,18 +415,18 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
       for (int ks = 0; ks < kKS; ++ks) {
         const int d0 = ks * 32 + lgrp * 8;
         const bf16x8 ka = *reinterpret_cast<const bf16x8*>(
-            swz_rm_at<D>(reinterpret_cast<char*>(k_lds), kv_row, d0));
+            swz_rm_at<DQK>(reinterpret_cast<char*>(k_lds), kv_row, d0));
 #pragma unroll
-        for (int m = 0; m < 2; ++m) st[m][nt] = mfma16(ka, q_frag[m][ks], st[m][nt]);
+        for (int m = 0; m < kM; ++m) st[m][nt] = mfma16(ka, q_frag[m][ks], st[m][nt]);
       }
     }
     __builtin_amdgcn_s_setprio(0);
 
     // ---- per-lane online softmax; P^T packed as PV's B operand -------------
-    bf16x8 pb[2][2];  // [m][ks2]
+    bf16x8 pb[kM][2];  // [m][ks2]
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int my_q_row = q_tile * kFwdQ + wave * 32 + m * 16;
+    for (int m = 0; m < kM; ++m) {
+      const int my_q_row = q_tile * FQ + wave * kWaveQ + m * 16;
       // Tile-level mask skip: most KV tiles sit fully below the causal
       // diagonal and inside the window for every row of this sub-tile -- the
       // per-element mask chain (3 compares + select x16) only runs on the
@@ -488,7 +526,7 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
         const bf16x8 va = *reinterpret_cast<const bf16x8*>(
             swz_t_at<kFwdKv>(reinterpret_cast<char*>(vt_lds), d, kv_off));
 #pragma unroll
-        for (int m = 0; m < 2; ++m) o_acc[m][nt] = mfma16(va, pb[m][ks2], o_acc[m][nt]);
+        for (int m = 0; m < kM; ++m) o_acc[m][nt] = mfma16(va, pb[m][ks2], o_acc[m][nt]);
       }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -503,24 +541,25 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
   // ---- epilogue: merge the per-lane l across each row's 4 lanes (once),
   // then O /= l; stage in LDS; coalesced 16B stores; LSE --------------------
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
+  for (int m = 0; m < kM; ++m) {
     // butterfly over the 16 column classes in the order c ^ 1, 2, 4, 8
     l_run[m][0] = (l_run[m][0] + l_run[m][1]) + (l_run[m][2] + l_run[m][3]);
     l_run[m][0] += __shfl_xor(l_run[m][0], 32, 64);
     l_run[m][0] += __shfl_xor(l_run[m][0], 16, 64);
   }
   {
-    // reuse: swizzled [64][D], staged twice (two 64-row halves)
+    // reuse: swizzled [64][DV], staged once per 64-row half of the q tile
     char* o_lds = reinterpret_cast<char*>(k_lds);
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
+    for (int half = 0; half < FQ / 64; ++half) {
       __syncthreads();
-      // waves 0,1 hold q rows 0..63 of the tile; waves 2,3 rows 64..127
-      if ((wave >> 1) == half) {
+      // FQ = 128: waves 0,1 hold q rows 0..63 of the tile; waves 2,3 rows
+      // 64..127. FQ = 64: every wave holds 16 rows of the one half.
+      if ((FQ == 128 ? (wave >> 1) : 0) == half) {
 #pragma unroll
-        for (int m = 0; m < 2; ++m) {
+        for (int m = 0; m < kM; ++m) {
           const float inv_l = (l_run[m][0] > 0.f) ? 1.f / l_run[m][0] : 0.f;
-          const int row = (wave & 1) * 32 + m * 16 + lrow;
+          const int row = (FQ == 128 ? (wave & 1) * 32 : wave * 16) + m * 16 + lrow;
 #pragma unroll
           for (int nt = 0; nt < kNT; ++nt) {
             bf16x4_bits o4;  // 4 consecutive d of one row
@@ -528,27 +567,62 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
             for (int r = 0; r < 4; ++r)
               o4.s[r] = bf16_bits((bf16_t)(o_acc[m][nt][r] * inv_l));
             *reinterpret_cast<uint64_t*>(
-                swz_rm_at<D>(o_lds, row, nt * 16 + lgrp * 4)) = o4.u;
+                swz_rm_at<DV>(o_lds, row, nt * 16 + lgrp * 4)) = o4.u;
           }
         }
       }
       __syncthreads();
-      constexpr int elems = 64 * D;
+      constexpr int elems = 64 * DV;
       for (int idx = threadIdx.x * 8; idx < elems; idx += 256 * 8) {
-        const int row = idx / D;
-        const int col = idx % D;
-        const int rg = q_tile * kFwdQ + half * 64 + row;
+        const int row = idx / DV;
+        const int col = idx % DV;
+        const int rg = q_tile * FQ + half * 64 + row;
         if (rg < Sq_loc) {
           *reinterpret_cast<bf16x8*>(
-              out + q_base + (int64_t)(q_lo + rg) * q_row_stride + col) =
-              *reinterpret_cast<const bf16x8*>(swz_rm_at<D>(o_lds, row, col));
+              out + o_base + (int64_t)(q_lo + rg) * o_row_stride + col) =
+              *reinterpret_cast<const bf16x8*>(swz_rm_at<DV>(o_lds, row, col));
+        }
+      }
+      if constexpr (kOutLo) {
+        // Second plane of `out`: the bf16 rounding residual O - bf16(O), the
+        // same way through LDS. The backward adds it back in delta.
+        __syncthreads();
+        if ((FQ == 128 ? (wave >> 1) : 0) == half) {
+#pragma unroll
+          for (int m = 0; m < kM; ++m) {
+            const float inv_l = (l_run[m][0] > 0.f) ? 1.f / l_run[m][0] : 0.f;
+            const int row = (FQ == 128 ? (wave & 1) * 32 : wave * 16) + m * 16 + lrow;
+#pragma unroll
+            for (int nt = 0; nt < kNT; ++nt) {
+              bf16x4_bits o4;
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const float o = o_acc[m][nt][r] * inv_l;
+                o4.s[r] = bf16_bits((bf16_t)(o - (float)(bf16_t)o));
+              }
+              *reinterpret_cast<uint64_t*>(
+                  swz_rm_at<DV>(o_lds, row, nt * 16 + lgrp * 4)) = o4.u;
+            }
+          }
+        }
+        __syncthreads();
+        bf16_t* out_lo = out + (int64_t)B * Sq * Hq * DV;
+        for (int idx = threadIdx.x * 8; idx < elems; idx += 256 * 8) {
+          const int row = idx / DV;
+          const int col = idx % DV;
+          const int rg = q_tile * FQ + half * 64 + row;
+          if (rg < Sq_loc) {
+            *reinterpret_cast<bf16x8*>(
+                out_lo + o_base + (int64_t)(q_lo + rg) * o_row_stride + col) =
+                *reinterpret_cast<const bf16x8*>(swz_rm_at<DV>(o_lds, row, col));
+          }
         }
       }
     }
     if (lgrp == 0) {
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const int rg = q_tile * kFwdQ + wave * 32 + m * 16 + lrow;
+      for (int m = 0; m < kM; ++m) {
+        const int rg = q_tile * FQ + wave * kWaveQ + m * 16 + lrow;
         if (rg < Sq_loc) {
           // regular: (B,Hq,Sq); varlen: (Hq,total) with b == 0
           lse[((int64_t)b * Hq + h) * Sq + q_lo + rg] =
@@ -560,9 +634,9 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(
 }
 
 // K tile + V^T tile (the kernel's LDS carve-up).
-template <int D>
+template <int DQK, int DV>
 constexpr size_t fwd_smem_bytes() {
-  return sizeof(bf16_t) * (kFwdKv * D + D * kFwdKv);
+  return sizeof(bf16_t) * (kFwdKv * DQK + DV * kFwdKv);
 }
 
 // ---------------------------------------------------------------------------
@@ -592,16 +666,44 @@ __global__ void attn_delta_kernel(
   }
 }
 
+// The same with O given as its bf16 value plus its rounding residual (the
+// wide forward's second plane): delta = sum_d dO * (O + O_lo).
+__global__ void attn_delta_lo_kernel(
+    const bf16_t* __restrict__ dout,  // (B,Sq,Hq,D)
+    const bf16_t* __restrict__ out,
+    const bf16_t* __restrict__ out_lo,
+    float* __restrict__ delta,        // (B,Hq,Sq)
+    int B, int Sq, int Hq, int D) {
+  const int64_t row = blockIdx.x;  // over B*Sq*Hq
+  if (row >= (int64_t)B * Sq * Hq) return;
+  const int h = row % Hq;
+  const int s = (row / Hq) % Sq;
+  const int b = row / ((int64_t)Hq * Sq);
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < D; i += 64) {
+    acc += (float)dout[row * D + i] *
+           ((float)out[row * D + i] + (float)out_lo[row * D + i]);
+  }
+  acc = wave_reduce_sum(acc);
+  if (threadIdx.x == 0) {
+    delta[((int64_t)b * Hq + h) * Sq + s] = acc;
+  }
+}
+
 // P / dS images: kBwdKv / 16 blocks of 128 B per 4-q row, stride padded +32 B.
 constexpr int kBwdXStride = (kBwdKv / 16) * 128 + 32;
 
-// Q, dO, dO^T, Q^T tiles + K^T + the P and dS images.
-template <int D>
+// Q, dO, dO^T, Q^T tiles (QR q rows each) + K^T + the P and dS images. At
+// <192, 128> 64 q rows would need 164864 B, 1 KiB over a workgroup's 160 KiB;
+// 32 rows need 107008 B.
+template <int DQK, int DV, int QR>
 constexpr size_t bwd_smem_bytes() {
-  return sizeof(bf16_t) * (4 * kBwdQ * D + D * kBwdKv) + 2 * (kBwdQ / 4) * kBwdXStride;
+  return sizeof(bf16_t) * (2 * QR * DQK + 2 * QR * DV + DQK * kBwdKv) +
+         2 * (QR / 4) * kBwdXStride;
 }
 
-template <int D>
+// QR: q rows per staged Q/dO tile (kBwdQ, or kBwdQWide for the wide pair).
+template <int DQK, int DV, int QR>
 __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
     const bf16_t* __restrict__ q,
     const bf16_t* __restrict__ k,
@@ -609,18 +711,25 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
     const bf16_t* __restrict__ dout,
     const float* __restrict__ lse,    // (B,Hq,Sq)
     const float* __restrict__ delta,  // (B,Hq,Sq)
-    float* __restrict__ dq,           // (B,Sq,Hq,D) fp32 accum
-    float* __restrict__ dk,           // (B,Skv,Hkv,D) fp32 accum
-    float* __restrict__ dv,           // (B,Skv,Hkv,D) fp32 accum
+    float* __restrict__ dq,           // (B,Sq,Hq,DQK) fp32 accum
+    float* __restrict__ dk,           // (B,Skv,Hkv,DQK) fp32 accum
+    float* __restrict__ dv,           // (B,Skv,Hkv,DV) fp32 accum
     const int* __restrict__ cu_q,     // packed-seq bounds, or nullptr
     const int* __restrict__ cu_k,
     const int* __restrict__ kvtile_pref,  // prefix of ceil(len_k/kBwdKv)
     int nseq,
     int B, int Sq, int Skv, int Hq, int Hkv,
     float scale, int causal, int window_left, int q_offset) {
-  constexpr int kNT = D / 16;
-  constexpr int kKS = D / 32;
-  static_assert(kNT >= 2 && kNT % 2 == 0, "dQ splits the head dim in halves");
+  static_assert(DV <= DQK, "the loops over DQK carry the DV work along");
+  static_assert(QR == 64 || QR == 32, "q tile rows");
+  constexpr int kNT = DQK / 16;   // n-tiles over the qk head dim (dK, dQ)
+  constexpr int kKS = DQK / 32;   // k-steps over the qk head dim (S)
+  constexpr int kNTV = DV / 16;   // n-tiles over the v head dim (dV)
+  constexpr int kKSV = DV / 32;   // k-steps over the v head dim (dP)
+  constexpr int kQT = QR / 16;    // 16-row q m-tiles per staged tile
+  // dQ: the 8 waves split into kQT m-tiles x (8 / kQT) slices of the head dim
+  constexpr int kDqParts = 8 / kQT;
+  static_assert(kNT % kDqParts == 0, "dQ splits the head dim evenly");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // Separate buffers for every staged operand: the three MFMA phases
@@ -630,11 +739,11 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
   // schedule). 149 KB LDS at D=128 -- one workgroup per CU, which this
   // kernel is at anyway.
   // bwd_smem_bytes() is this carve-up.
-  bf16_t* q_lds = reinterpret_cast<bf16_t*>(smem);   // [64][D] swizzled rows
-  bf16_t* do_lds = q_lds + kBwdQ * D;                // [64][D]
-  bf16_t* tdo_lds = do_lds + kBwdQ * D;              // [D][64]: dO^T
-  bf16_t* tq_lds = tdo_lds + D * kBwdQ;              // [D][64]: Q^T
-  bf16_t* kt_lds = tq_lds + D * kBwdQ;               // [D][kBwdKv]
+  bf16_t* q_lds = reinterpret_cast<bf16_t*>(smem);   // [QR][DQK] swizzled rows
+  bf16_t* do_lds = q_lds + QR * DQK;                 // [QR][DV]
+  bf16_t* tdo_lds = do_lds + QR * DV;                // [DV][QR]: dO^T
+  bf16_t* tq_lds = tdo_lds + DV * QR;                // [DQK][QR]: Q^T
+  bf16_t* kt_lds = tq_lds + DQK * QR;                // [DQK][kBwdKv]
   // P and dS live in ONE q-major blocked image each: [4 q][16 kv] 128-B
   // tr16 blocks at (q>>2, kv>>4), qb stride padded +32 B so the packed
   // b64 stores of 4 kv values per (q, nt) are bank-spread. dV/dK read
@@ -642,8 +751,8 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
   // q-major fragments as plain 16-B rows of the SAME dS image — the old
   // third (q-major) copy and 48 scalar stores per wave are gone.
   constexpr int kXqStride = kBwdXStride;             // bytes per q-block row
-  char* x1_lds = reinterpret_cast<char*>(kt_lds + D * kBwdKv);  // P image
-  char* x2_lds = x1_lds + (kBwdQ / 4) * kXqStride;              // dS image
+  char* x1_lds = reinterpret_cast<char*>(kt_lds + DQK * kBwdKv);  // P image
+  char* x2_lds = x1_lds + (QR / 4) * kXqStride;                   // dS image
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;   // 8 waves x 16 kv rows = 128 kv/block
@@ -656,10 +765,15 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
   const int q_lo = loc.q_lo, Sq_loc = loc.Sq_loc, kv_lo = loc.kv_lo, Skv_loc = loc.Skv_loc;
   const int hkv = h / (Hq / Hkv);
 
-  const int64_t q_base = ((int64_t)b * Sq * Hq + h) * D;
-  const int64_t kv_base = ((int64_t)b * Skv * Hkv + hkv) * D;
-  const int64_t q_row_stride = (int64_t)Hq * D;
-  const int64_t kv_row_stride = (int64_t)Hkv * D;
+  const int64_t q_base = ((int64_t)b * Sq * Hq + h) * DQK;
+  const int64_t kv_base = ((int64_t)b * Skv * Hkv + hkv) * DQK;
+  const int64_t q_row_stride = (int64_t)Hq * DQK;
+  const int64_t kv_row_stride = (int64_t)Hkv * DQK;
+  // the same for the DV-wide tensors (dout; v, dv); one value where DQK == DV
+  const int64_t o_base = DQK == DV ? q_base : ((int64_t)b * Sq * Hq + h) * DV;
+  const int64_t v_base = DQK == DV ? kv_base : ((int64_t)b * Skv * Hkv + hkv) * DV;
+  const int64_t o_row_stride = DQK == DV ? q_row_stride : (int64_t)Hq * DV;
+  const int64_t v_row_stride = DQK == DV ? kv_row_stride : (int64_t)Hkv * DV;
   const float* lse_row = lse + ((int64_t)b * Hq + h) * Sq + q_lo;
   const float* delta_row = delta + ((int64_t)b * Hq + h) * Sq + q_lo;
 
@@ -669,68 +783,82 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
   const int kv_row_local = lane & 15;
   const int kv_row_global =
       kv_lo + min(kv0 + wave * 16 + kv_row_local, Skv_loc - 1);
-  bf16x8 k_frag[kKS], v_frag[kKS];
+  bf16x8 k_frag[kKS], v_frag[kKSV];
   {
     const bf16_t* kp = k + kv_base + (int64_t)kv_row_global * kv_row_stride;
-    const bf16_t* vp = v + kv_base + (int64_t)kv_row_global * kv_row_stride;
+    const bf16_t* vp = v + v_base + (int64_t)kv_row_global * v_row_stride;
 #pragma unroll
     for (int ks = 0; ks < kKS; ++ks) {
       const int d0 = ks * 32 + (lane >> 4) * 8;
       k_frag[ks] = *reinterpret_cast<const bf16x8*>(kp + d0);
-      v_frag[ks] = *reinterpret_cast<const bf16x8*>(vp + d0);
+      if (ks < kKSV) v_frag[ks] = *reinterpret_cast<const bf16x8*>(vp + d0);
     }
   }
 
   // Stage K^T once (for dQ's B fragments).
-  stage_transposed_tile<D, kBwdKv, kBwdThreads>(
+  stage_transposed_tile<DQK, kBwdKv, kBwdThreads>(
       kt_lds, k + kv_base, kv_row_stride, kv_lo, kv0, Skv_loc - 1, threadIdx.x);
 
-  f32x4 dk_acc[kNT], dv_acc[kNT];
+  f32x4 dk_acc[kNT], dv_acc[kNTV];
 #pragma unroll
   for (int nt = 0; nt < kNT; ++nt) {
     dk_acc[nt] = {0.f, 0.f, 0.f, 0.f};
-    dv_acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    if (nt < kNTV) dv_acc[nt] = {0.f, 0.f, 0.f, 0.f};
   }
 
   int q_start = 0;
   if (causal) {
     // first q tile whose last aligned position reaches kv0
-    q_start = (max(kv0 - causal_off, 0) / kBwdQ) * kBwdQ;
+    q_start = (max(kv0 - causal_off, 0) / QR) * QR;
   }
   if (q_start >= Sq_loc) return;
 
   // T14: each q-tile's Q/dO rows are prefetched into registers while the
   // previous tile's MFMAs run; the transposed images are derived from the
   // row-major LDS copies (cheap ds_reads) instead of re-reading global.
-  constexpr int kQdoRegs =
-      (kBwdQ * D + kBwdThreads * 8 - 1) / (kBwdThreads * 8);  // >= 1 (D <= 128)
-  bf16x8 q_reg[kQdoRegs], do_reg[kQdoRegs];
+  // Work item idx is an 8-element group of the [QR][DQK] Q tile and, while
+  // idx < QR * DV, of the narrower [QR][DV] dO tile as well.
+  constexpr int kQRegs =
+      (QR * DQK + kBwdThreads * 8 - 1) / (kBwdThreads * 8);  // >= 1
+  constexpr int kDoRegs = (QR * DV + kBwdThreads * 8 - 1) / (kBwdThreads * 8);
+  bf16x8 q_reg[kQRegs], do_reg[kDoRegs];
 
   auto load_qdo_regs = [&](int qt_next) {
 #pragma unroll
-    for (int it = 0; it < kQdoRegs; ++it) {
+    for (int it = 0; it < kQRegs; ++it) {
       const int idx = (threadIdx.x + it * kBwdThreads) * 8;
-      if (idx >= kBwdQ * D) break;
-      const int row = idx / D;
-      const int col = idx % D;
+      if (idx >= QR * DQK) break;
+      const int row = idx / DQK;
+      const int col = idx % DQK;
       const int g_row = q_lo + min(qt_next + row, Sq_loc - 1);
       q_reg[it] = *reinterpret_cast<const bf16x8*>(
           q + q_base + (int64_t)g_row * q_row_stride + col);
-      do_reg[it] = *reinterpret_cast<const bf16x8*>(
-          dout + q_base + (int64_t)g_row * q_row_stride + col);
+      if constexpr (DQK == DV) {
+        do_reg[it] = *reinterpret_cast<const bf16x8*>(
+            dout + q_base + (int64_t)g_row * q_row_stride + col);
+      } else if (it < kDoRegs && idx < QR * DV) {
+        const int o_row = q_lo + min(qt_next + idx / DV, Sq_loc - 1);
+        do_reg[it] = *reinterpret_cast<const bf16x8*>(
+            dout + o_base + (int64_t)o_row * o_row_stride + idx % DV);
+      }
     }
   };
   auto store_qdo_lds = [&]() {
 #pragma unroll
-    for (int it = 0; it < kQdoRegs; ++it) {
+    for (int it = 0; it < kQRegs; ++it) {
       const int idx = (threadIdx.x + it * kBwdThreads) * 8;
-      if (idx >= kBwdQ * D) break;
-      const int row = idx / D;
-      const int col = idx % D;
+      if (idx >= QR * DQK) break;
+      const int row = idx / DQK;
+      const int col = idx % DQK;
       *reinterpret_cast<bf16x8*>(
-          swz_rm_at<D>(reinterpret_cast<char*>(q_lds), row, col)) = q_reg[it];
-      *reinterpret_cast<bf16x8*>(
-          swz_rm_at<D>(reinterpret_cast<char*>(do_lds), row, col)) = do_reg[it];
+          swz_rm_at<DQK>(reinterpret_cast<char*>(q_lds), row, col)) = q_reg[it];
+      if constexpr (DQK == DV) {
+        *reinterpret_cast<bf16x8*>(
+            swz_rm_at<DV>(reinterpret_cast<char*>(do_lds), row, col)) = do_reg[it];
+      } else if (it < kDoRegs && idx < QR * DV) {
+        *reinterpret_cast<bf16x8*>(swz_rm_at<DV>(
+            reinterpret_cast<char*>(do_lds), idx / DV, idx % DV)) = do_reg[it];
+      }
     }
   };
 
@@ -738,28 +866,28 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
   store_qdo_lds();
   __syncthreads();
 
-  for (int qt = q_start; qt < Sq_loc; qt += kBwdQ) {
-    if (qt + kBwdQ < Sq_loc) load_qdo_regs(qt + kBwdQ);  // issue early
+  for (int qt = q_start; qt < Sq_loc; qt += QR) {
+    if (qt + QR < Sq_loc) load_qdo_regs(qt + QR);  // issue early
     // dO^T and Q^T images for the dV/dK B fragments (cheap LDS-to-LDS).
     // NO barrier here: tdo/tq are first read after the x-stage barrier
     // below, which also publishes these writes (2 barriers per q-tile
     // instead of 4 — the PMC wave-parked share was the top bwd cost).
-    transpose_lds_tile<D, kBwdThreads>(tdo_lds, do_lds, threadIdx.x);
-    transpose_lds_tile<D, kBwdThreads>(tq_lds, q_lds, threadIdx.x);
+    transpose_lds_tile<DV, QR, kBwdThreads>(tdo_lds, do_lds, threadIdx.x);
+    transpose_lds_tile<DQK, QR, kBwdThreads>(tq_lds, q_lds, threadIdx.x);
 
-    // ---- S^T = K @ Q^T (per wave: 16 kv x 64 q) ----------------------------
-    f32x4 st_acc[4];
+    // ---- S^T = K @ Q^T (per wave: 16 kv x QR q) ----------------------------
+    f32x4 st_acc[kQT];
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) st_acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    for (int nt = 0; nt < kQT; ++nt) st_acc[nt] = {0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
+    for (int nt = 0; nt < kQT; ++nt) {
       const int q_row = nt * 16 + (lane & 15);
 #pragma unroll
       for (int ks = 0; ks < kKS; ++ks) {
         const int d0 = ks * 32 + (lane >> 4) * 8;
         const bf16x8 qb = *reinterpret_cast<const bf16x8*>(
-            swz_rm_at<D>(reinterpret_cast<char*>(q_lds), q_row, d0));
+            swz_rm_at<DQK>(reinterpret_cast<char*>(q_lds), q_row, d0));
         st_acc[nt] = mfma16(k_frag[ks], qb, st_acc[nt]);
       }
     }
@@ -769,14 +897,14 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
     // Tile-level mask skip (see fwd): interior tiles take the select-free
     // path, only diagonal/edge tiles run the per-element mask chain.
     const bool any_mask =
-        (kv0 + kBwdKv > Skv_loc) || (qt + kBwdQ > Sq_loc) ||
+        (kv0 + kBwdKv > Skv_loc) || (qt + QR > Sq_loc) ||
         (causal && kv0 + kBwdKv - 1 > qt + causal_off) ||
         (window_left >= 0 &&
-         kv0 < qt + kBwdQ - 1 + causal_off - window_left);
-    float pt_val[4][4];  // [nt][r]
+         kv0 < qt + QR - 1 + causal_off - window_left);
+    float pt_val[kQT][4];  // [nt][r]
     if (any_mask) {
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
+      for (int nt = 0; nt < kQT; ++nt) {
         const int q_glob = qt + nt * 16 + (lane & 15);
         const float l = (q_glob < Sq_loc) ? lse_row[min(q_glob, Sq_loc - 1)] : 1e30f;
 #pragma unroll
@@ -792,7 +920,7 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
       }
     } else {
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
+      for (int nt = 0; nt < kQT; ++nt) {
         // clamp even on the fast path: the compiler may speculate this load
         // across the branch, and edge tiles would read past the lse buffer
         const float l = lse_row[min(qt + nt * 16 + (lane & 15), Sq_loc - 1)];
@@ -805,27 +933,27 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
     }
 
     // ---- dP^T = V @ dO^T ---------------------------------------------------
-    f32x4 dpt_acc[4];
+    f32x4 dpt_acc[kQT];
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) dpt_acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    for (int nt = 0; nt < kQT; ++nt) dpt_acc[nt] = {0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
+    for (int nt = 0; nt < kQT; ++nt) {
       const int q_row = nt * 16 + (lane & 15);
 #pragma unroll
-      for (int ks = 0; ks < kKS; ++ks) {
+      for (int ks = 0; ks < kKSV; ++ks) {
         const int d0 = ks * 32 + (lane >> 4) * 8;
         const bf16x8 db = *reinterpret_cast<const bf16x8*>(
-            swz_rm_at<D>(reinterpret_cast<char*>(do_lds), q_row, d0));
+            swz_rm_at<DV>(reinterpret_cast<char*>(do_lds), q_row, d0));
         dpt_acc[nt] = mfma16(v_frag[ks], db, dpt_acc[nt]);
       }
     }
     __builtin_amdgcn_s_setprio(0);
 
     // ---- dS^T = P^T * (dP^T - delta[q]) * scale ---------------------------
-    float dst_val[4][4];
+    float dst_val[kQT][4];
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
+    for (int nt = 0; nt < kQT; ++nt) {
       const int q_glob = qt + nt * 16 + (lane & 15);
       const float dlt = (q_glob < Sq_loc) ? delta_row[min(q_glob, Sq_loc - 1)] : 0.f;
 #pragma unroll
@@ -839,7 +967,7 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
     // the 4 r-values (4 consecutive kv at fixed q) pack into one b64 store.
     {
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
+      for (int nt = 0; nt < kQT; ++nt) {
         const int q_l = nt * 16 + (lane & 15);
         const int kv_l = wave * 16 + (lane >> 4) * 4;
         const size_t byte = (size_t)(q_l >> 2) * kXqStride +
@@ -875,18 +1003,21 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
       };
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
+      for (int ks2 = 0; ks2 < QR / 32; ++ks2) {
         const int q_off = ks2 * 32 + (lane >> 4) * 8;
         const bf16x8 pa = xfrag(x1_lds, q_off);
         const bf16x8 da = xfrag(x2_lds, q_off);
 #pragma unroll
         for (int nt = 0; nt < kNT; ++nt) {
           const int d = nt * 16 + (lane & 15);
-          const bf16x8 dob = *reinterpret_cast<const bf16x8*>(
-              swz_t_at<kBwdQ>(reinterpret_cast<char*>(tdo_lds), d, q_off));
+          bf16x8 dob;  // dV has DV / 16 n-tiles, dK DQK / 16
+          if (nt < kNTV) {
+            dob = *reinterpret_cast<const bf16x8*>(
+                swz_t_at<QR>(reinterpret_cast<char*>(tdo_lds), d, q_off));
+          }
           const bf16x8 qb = *reinterpret_cast<const bf16x8*>(
-              swz_t_at<kBwdQ>(reinterpret_cast<char*>(tq_lds), d, q_off));
-          dv_acc[nt] = mfma16(pa, dob, dv_acc[nt]);
+              swz_t_at<QR>(reinterpret_cast<char*>(tq_lds), d, q_off));
+          if (nt < kNTV) dv_acc[nt] = mfma16(pa, dob, dv_acc[nt]);
           dk_acc[nt] = mfma16(da, qb, dk_acc[nt]);
         }
       }
@@ -897,10 +1028,11 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
     {
       // ALL 8 waves: wave & 3 picks the 16-row q m-tile, wave >> 2 the
       // d-half -- the old waves-0-3-only split parked half the block
-      // through an entire MFMA phase.
-      constexpr int kNTH = kNT / 2;  // nt per d-half
-      const int q_mt = wave & 3;
-      const int nt0 = (wave >> 2) * kNTH;
+      // through an entire MFMA phase. (32 q rows: wave & 1 and the d-quarter
+      // wave >> 1.)
+      constexpr int kNTH = kNT / kDqParts;  // nt per d-slice
+      const int q_mt = wave & (kQT - 1);
+      const int nt0 = (wave >> (kQT == 4 ? 2 : 1)) * kNTH;
       f32x4 dq_acc[kNTH];
 #pragma unroll
       for (int nt = 0; nt < kNTH; ++nt) dq_acc[nt] = {0.f, 0.f, 0.f, 0.f};
@@ -939,7 +1071,7 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
     // them reads q_lds/do_lds (their consumers — S^T, dP^T and the
     // transposes — all ran before the x-stage barrier), so the write only
     // needs the end-of-iteration barrier to publish for the next tile.
-    if (qt + kBwdQ < Sq_loc) {
+    if (qt + QR < Sq_loc) {
       store_qdo_lds();
     }
     __syncthreads();
@@ -955,8 +1087,10 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
         const int d = nt * 16 + (lane & 15);
         atomicAdd(dk + kv_base + (int64_t)(kv_lo + kv_glob) * kv_row_stride + d,
                   dk_acc[nt][r]);
-        atomicAdd(dv + kv_base + (int64_t)(kv_lo + kv_glob) * kv_row_stride + d,
-                  dv_acc[nt][r]);
+        if (nt < kNTV) {
+          atomicAdd(dv + v_base + (int64_t)(kv_lo + kv_glob) * v_row_stride + d,
+                    dv_acc[nt][r]);
+        }
       }
     }
   }
@@ -1065,12 +1199,21 @@ __global__ void cast3_f32_bf16_kernel(
 
 namespace {
 
-int padded_head_dim(int d) {
+// The instantiated <DQK, DV> pair a (qk, v) head-dim pair is padded to: one
+// common D in {32, 64, 96, 128} while both fit, else the wide pair.
+struct HeadDims {
+  int qk, v;
+};
+
+HeadDims padded_head_dims(int d_qk, int d_v) {
+  const int d = std::max(d_qk, d_v);
   for (int cand : {32, 64, 96, 128}) {
-    if (d <= cand) return cand;
+    if (d <= cand) return {cand, cand};
   }
-  TORCH_CHECK(false, "head_dim too large: ", d);
-  return -1;
+  TORCH_CHECK(d_qk <= 192 && d_v <= 128,
+              "flash attention supports qk head_dim <= 192 with v head_dim <= "
+              "128; got qk ", d_qk, ", v ", d_v);
+  return {192, 128};
 }
 
 torch::Tensor maybe_pad_d(torch::Tensor t, int D_pad) {
@@ -1117,14 +1260,17 @@ VarlenMeta prepare_varlen(const c10::optional<torch::Tensor>& cu_seqlens_q,
   return m;
 }
 
-// Calls f(std::integral_constant<int, D_pad>) for the instantiated head dims.
+// Calls f(integral_constant<DQK>, integral_constant<DV>) for the instantiated
+// pairs (what padded_head_dims returns).
 template <typename F>
-void dispatch_head_dim(int D_pad, F&& f) {
-  switch (D_pad) {
-    case 32: f(std::integral_constant<int, 32>{}); break;
-    case 64: f(std::integral_constant<int, 64>{}); break;
-    case 96: f(std::integral_constant<int, 96>{}); break;
-    case 128: f(std::integral_constant<int, 128>{}); break;
+void dispatch_head_dims(HeadDims d, F&& f) {
+  using std::integral_constant;
+  switch (d.qk) {
+    case 32: f(integral_constant<int, 32>{}, integral_constant<int, 32>{}); break;
+    case 64: f(integral_constant<int, 64>{}, integral_constant<int, 64>{}); break;
+    case 96: f(integral_constant<int, 96>{}, integral_constant<int, 96>{}); break;
+    case 128: f(integral_constant<int, 128>{}, integral_constant<int, 128>{}); break;
+    case 192: f(integral_constant<int, 192>{}, integral_constant<int, 128>{}); break;
   }
 }
 
@@ -1146,18 +1292,25 @@ std::vector<torch::Tensor> flash_attn_fwd(
   }
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4);
   const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Skv = k.size(1), Hkv = k.size(2);
+  const int Skv = k.size(1), Hkv = k.size(2), Dv = v.size(3);
   TORCH_CHECK(Hq % Hkv == 0, "GQA head mismatch");
+  TORCH_CHECK(k.size(3) == D && v.size(1) == Skv && v.size(2) == Hkv,
+              "flash_attn_fwd: k/v shape mismatch");
 
-  const int D_pad = padded_head_dim(D);
-  auto qp = maybe_pad_d(q, D_pad);
-  auto kp = maybe_pad_d(k, D_pad);
-  auto vp = maybe_pad_d(v, D_pad);
+  const HeadDims pad = padded_head_dims(D, Dv);
+  auto qp = maybe_pad_d(q, pad.qk);
+  auto kp = maybe_pad_d(k, pad.qk);
+  auto vp = maybe_pad_d(v, pad.v);
 
-  const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, d9d::kFwdQ,
+  const int fq = pad.qk > 128 ? d9d::kFwdQWide : d9d::kFwdQ;  // q rows per workgroup
+  const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, fq,
                                        /*tile_kv=*/false, q.device());
 
-  auto out = torch::empty_like(qp);
+  // the wide pair writes a second plane: O's bf16 rounding residual
+  const bool wide = pad.qk > 128;
+  auto out2 = wide ? torch::empty({2, B, Sq, Hq, (int64_t)pad.v}, qp.options())
+                   : torch::empty({B, Sq, Hq, (int64_t)pad.v}, qp.options());
+  auto out = wide ? out2.select(0, 0) : out2;
   auto lse = torch::empty({varlen ? 1 : B, Hq, Sq},
                           q.options().dtype(torch::kFloat32));
   const float* sinks_ptr = nullptr;
@@ -1168,30 +1321,36 @@ std::vector<torch::Tensor> flash_attn_fwd(
     sinks_ptr = sinks_f.data_ptr<float>();
   }
 
-  const dim3 grid(varlen ? vl.n_tiles : (Sq + d9d::kFwdQ - 1) / d9d::kFwdQ,
+  const dim3 grid(varlen ? vl.n_tiles : (Sq + fq - 1) / fq,
                   varlen ? Hq : B * Hq);
   auto stream = at::hip::getCurrentHIPStream();
 
-  dispatch_head_dim(D_pad, [&](auto dp) {
-    constexpr int DP = decltype(dp)::value;
-    hipLaunchKernelGGL((d9d::flash_fwd_kernel<DP>), grid, dim3(256),
-                       d9d::fwd_smem_bytes<DP>(), stream,
+  dispatch_head_dims(pad, [&](auto dqk, auto dv) {
+    constexpr int DQK = decltype(dqk)::value, DV = decltype(dv)::value;
+    constexpr int FQ = DQK > 128 ? d9d::kFwdQWide : d9d::kFwdQ;
+    hipLaunchKernelGGL((d9d::flash_fwd_kernel<DQK, DV, FQ>), grid, dim3(256),
+                       (d9d::fwd_smem_bytes<DQK, DV>()), stream,
                        reinterpret_cast<const __bf16*>(qp.data_ptr()),
                        reinterpret_cast<const __bf16*>(kp.data_ptr()),
                        reinterpret_cast<const __bf16*>(vp.data_ptr()),
-                       reinterpret_cast<__bf16*>(out.data_ptr()),
+                       reinterpret_cast<__bf16*>(out2.data_ptr()),
                        lse.data_ptr<float>(), sinks_ptr, vl.cu_q_ptr,
                        vl.cu_k_ptr, vl.pref_ptr, vl.nseq, B, Sq, Skv, Hq, Hkv,
                        (float)softmax_scale, causal ? 1 : 0, (int)window_left,
                        (int)q_offset);
   });
 
-  if (D_pad != D) out = out.narrow(-1, 0, D).contiguous();
+  if (pad.v != Dv) out = out.narrow(-1, 0, Dv).contiguous();
   if (varlen) {
     out = out.squeeze(0);
     lse = lse.squeeze(0);  // (Hq, total)
   }
-  return {out, lse};
+  if (!wide) return {out, lse};
+  // third result, wide pair only: the residual, for flash_attn_bwd's out_lo
+  auto out_lo = out2.select(0, 1);
+  if (pad.v != Dv) out_lo = out_lo.narrow(-1, 0, Dv).contiguous();
+  if (varlen) out_lo = out_lo.squeeze(0);
+  return {out, lse, out_lo};
 }
 
 std::vector<torch::Tensor> flash_attn_bwd(
@@ -1200,9 +1359,10 @@ std::vector<torch::Tensor> flash_attn_bwd(
     c10::optional<torch::Tensor> cu_seqlens_q,
     c10::optional<torch::Tensor> cu_seqlens_k,
     bool causal, double softmax_scale, int64_t window_left, int64_t q_offset,
-    c10::optional<torch::Tensor> dlse) {
+    c10::optional<torch::Tensor> dlse, c10::optional<torch::Tensor> out_lo) {
   const bool varlen = cu_seqlens_q.has_value();
   if (varlen) {
+    if (out_lo.has_value()) out_lo = out_lo->unsqueeze(0);
     dout = dout.unsqueeze(0);
     q = q.unsqueeze(0);
     k = k.unsqueeze(0);
@@ -1211,37 +1371,51 @@ std::vector<torch::Tensor> flash_attn_bwd(
     lse = lse.unsqueeze(0);
   }
   const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Skv = k.size(1), Hkv = k.size(2);
-  const int D_pad = padded_head_dim(D);
+  const int Skv = k.size(1), Hkv = k.size(2), Dv = v.size(3);
+  TORCH_CHECK(k.size(3) == D && out.size(3) == Dv && dout.size(3) == Dv,
+              "flash_attn_bwd: k is as wide as q; out and dout as wide as v");
+  const HeadDims pad = padded_head_dims(D, Dv);
 
   const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, d9d::kBwdKv,
                                        /*tile_kv=*/true, q.device());
 
-  auto qp = maybe_pad_d(q, D_pad);
-  auto kp = maybe_pad_d(k, D_pad);
-  auto vp = maybe_pad_d(v, D_pad);
-  auto dop = maybe_pad_d(dout, D_pad);
-  auto op = maybe_pad_d(out, D_pad);
+  auto qp = maybe_pad_d(q, pad.qk);
+  auto kp = maybe_pad_d(k, pad.qk);
+  auto vp = maybe_pad_d(v, pad.v);
+  auto dop = maybe_pad_d(dout, pad.v);
+  auto op = maybe_pad_d(out, pad.v);
 
   auto f32opt = q.options().dtype(torch::kFloat32);
   auto delta = torch::empty({B, Hq, Sq}, f32opt);
   // atomicAdd accumulators: cleared via the copy/DMA engine (hipMemsetAsync)
   // instead of torch::zeros — the fill kernels measured ~1.7 TB/s in-step
   // and 400 MB/call of clears showed up at ~1.3% of the whole bench step.
-  auto dq32 = torch::empty({B, Sq, Hq, D_pad}, f32opt);
-  auto dk32 = torch::empty({B, Skv, Hkv, D_pad}, f32opt);
-  auto dv32 = torch::empty({B, Skv, Hkv, D_pad}, f32opt);
+  auto dq32 = torch::empty({B, Sq, Hq, pad.qk}, f32opt);
+  auto dk32 = torch::empty({B, Skv, Hkv, pad.qk}, f32opt);
+  auto dv32 = torch::empty({B, Skv, Hkv, pad.v}, f32opt);
 
   auto stream = at::hip::getCurrentHIPStream();
   hipMemsetAsync(dq32.data_ptr(), 0, dq32.numel() * sizeof(float), stream);
   hipMemsetAsync(dk32.data_ptr(), 0, dk32.numel() * sizeof(float), stream);
   hipMemsetAsync(dv32.data_ptr(), 0, dv32.numel() * sizeof(float), stream);
-  {
+  if (out_lo.has_value()) {
+    // O = out + out_lo (the wide forward's residual): delta as from an fp32 O
+    TORCH_CHECK(out_lo->sizes() == out.sizes() && out_lo->is_cuda() &&
+                    out_lo->scalar_type() == torch::kBFloat16,
+                "flash_attn_bwd: out_lo must match out");
+    auto olp = maybe_pad_d(*out_lo, pad.v);
+    const int64_t rows = (int64_t)B * Sq * Hq;
+    hipLaunchKernelGGL(d9d::attn_delta_lo_kernel, dim3(rows), dim3(64), 0, stream,
+                       reinterpret_cast<const __bf16*>(dop.data_ptr()),
+                       reinterpret_cast<const __bf16*>(op.data_ptr()),
+                       reinterpret_cast<const __bf16*>(olp.data_ptr()),
+                       delta.data_ptr<float>(), B, Sq, Hq, pad.v);
+  } else {
     const int64_t rows = (int64_t)B * Sq * Hq;
     hipLaunchKernelGGL(d9d::attn_delta_kernel, dim3(rows), dim3(64), 0, stream,
                        reinterpret_cast<const __bf16*>(dop.data_ptr()),
                        reinterpret_cast<const __bf16*>(op.data_ptr()),
-                       delta.data_ptr<float>(), B, Sq, Hq, D_pad);
+                       delta.data_ptr<float>(), B, Sq, Hq, pad.v);
   }
   if (dlse.has_value()) {
     // lse is itself an output: d(lse_i)/d(S_ij) = P_ij, so its upstream grad
@@ -1255,10 +1429,13 @@ std::vector<torch::Tensor> flash_attn_bwd(
 
   const dim3 grid(varlen ? vl.n_tiles : (Skv + d9d::kBwdKv - 1) / d9d::kBwdKv,
                   varlen ? Hq : B * Hq);
-  dispatch_head_dim(D_pad, [&](auto dp) {
-    constexpr int DP = decltype(dp)::value;
-    hipLaunchKernelGGL((d9d::flash_bwd_kernel<DP>), grid,
-                       dim3(d9d::kBwdThreads), d9d::bwd_smem_bytes<DP>(), stream,
+  dispatch_head_dims(pad, [&](auto dqk, auto dv_c) {
+    constexpr int DQK = decltype(dqk)::value, DV = decltype(dv_c)::value;
+    constexpr int QR = DQK > 128 ? d9d::kBwdQWide : d9d::kBwdQ;
+    constexpr size_t smem = d9d::bwd_smem_bytes<DQK, DV, QR>();
+    static_assert(smem <= 160 * 1024, "over a workgroup's LDS");
+    hipLaunchKernelGGL((d9d::flash_bwd_kernel<DQK, DV, QR>), grid,
+                       dim3(d9d::kBwdThreads), smem, stream,
                        reinterpret_cast<const __bf16*>(qp.data_ptr()),
                        reinterpret_cast<const __bf16*>(kp.data_ptr()),
                        reinterpret_cast<const __bf16*>(vp.data_ptr()),
@@ -1272,7 +1449,7 @@ std::vector<torch::Tensor> flash_attn_bwd(
   });
 
   torch::Tensor dq, dk, dv;
-  if (D == D_pad) {
+  if (D == pad.qk && Dv == pad.v) {
     // one fused cast launch for all three accumulators
     auto bf = q.options().dtype(torch::kBFloat16);
     dq = torch::empty(dq32.sizes(), bf);
@@ -1291,7 +1468,7 @@ std::vector<torch::Tensor> flash_attn_bwd(
   } else {
     dq = dq32.narrow(-1, 0, D).to(torch::kBFloat16).contiguous();
     dk = dk32.narrow(-1, 0, D).to(torch::kBFloat16).contiguous();
-    dv = dv32.narrow(-1, 0, D).to(torch::kBFloat16).contiguous();
+    dv = dv32.narrow(-1, 0, Dv).to(torch::kBFloat16).contiguous();
   }
   if (varlen) {
     dq = dq.squeeze(0);

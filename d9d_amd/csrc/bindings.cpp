@@ -30,7 +30,8 @@ std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q, t
                                           c10::optional<torch::Tensor> cu_seqlens_q,
                                           c10::optional<torch::Tensor> cu_seqlens_k,
                                           bool causal, double softmax_scale, int64_t window_left,
-                                          int64_t q_offset, c10::optional<torch::Tensor> dlse);
+                                          int64_t q_offset, c10::optional<torch::Tensor> dlse,
+                                          c10::optional<torch::Tensor> out_lo);
 torch::Tensor mfma_selfcheck(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma_chain_selfcheck(torch::Tensor a1, torch::Tensor b1, torch::Tensor a2);
 
@@ -126,7 +127,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_csr_combine", &moe_csr_combine, "MoE weighted replica combine");
   m.def("moe_row_dot", &moe_row_dot, "per-row dot for prob grads");
   m.def("flash_attn_fwd", &flash_attn_fwd, "CDNA4 flash attention forward");
-  m.def("flash_attn_bwd", &flash_attn_bwd, "CDNA4 flash attention backward");
+  m.def("flash_attn_bwd", &flash_attn_bwd, "CDNA4 flash attention backward",
+        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
+        py::arg("lse"), py::arg("cu_seqlens_q"), py::arg("cu_seqlens_k"),
+        py::arg("causal"), py::arg("softmax_scale"), py::arg("window_left"),
+        py::arg("q_offset"), py::arg("dlse"), py::arg("out_lo") = py::none());
   m.def("mfma_selfcheck", &mfma_selfcheck, "MFMA fragment-map self check");
   m.def("mfma_chain_selfcheck", &mfma_chain_selfcheck,
         "MFMA chained-fragment (C registers as B operand) self check");

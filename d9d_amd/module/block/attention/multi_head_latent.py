@@ -3,8 +3,10 @@
 Reference: d9d/module/block/attention/multi_head_latent.py — optional
 low-rank Q projection, KV down-projection to `kv_lora_rank` plus a shared
 rope sub-vector, RMSNorm on the latents, up-projection to per-head
-(qk_nope + v); V is zero-padded to the qk head dim so the flash kernel's
-uniform head_dim applies (reference notes this at :197).
+(qk_nope + v). Up to a qk head dim of 128 V is zero-padded to the qk head dim
+so the flash kernel's uniform head_dim applies (reference notes this at :197);
+wider (the DeepSeek default, qk 192 / v 128) the flash kernel's <192, 128>
+pair takes q/k and v at their own widths.
 """
 
 import math
@@ -94,6 +96,7 @@ class MultiHeadLatentAttention(nn.Module):
         self,
         hidden_states: torch.Tensor,  # (B, S, H)
         rotary_cos_sin: tuple[torch.Tensor, torch.Tensor],
+        cu_seqlens: torch.Tensor | None = None,  # packed documents (B == 1)
     ) -> torch.Tensor:
         B, S, _ = hidden_states.shape
         H = self.num_heads
@@ -118,8 +121,10 @@ class MultiHeadLatentAttention(nn.Module):
 
         q_full = torch.cat([q_nope, q_rope], dim=-1)
         k_full = torch.cat([k_nope, k_rope], dim=-1)
-        # pad V to qk_head_dim so one flash call handles both
-        if self.v_head_dim < self.qk_head_dim:
+        # up to qk_head_dim 128 pad V to qk_head_dim so one flash call handles
+        # both; past it (the default 192 / 128) the kernel runs over the two
+        # head dims as they are and V goes in unpadded
+        if self.v_head_dim < self.qk_head_dim <= 128:
             v_pad = torch.zeros(
                 B, S, H, self.qk_head_dim - self.v_head_dim,
                 device=v.device, dtype=v.dtype,
@@ -127,9 +132,22 @@ class MultiHeadLatentAttention(nn.Module):
             v_in = torch.cat([v, v_pad], dim=-1)
         else:
             v_in = v
-        attn = flash_attn_func(
-            q_full, k_full.contiguous(), v_in.contiguous(), causal=True,
-            softmax_scale=1.0 / math.sqrt(self.qk_head_dim),
-        )
+        scale = 1.0 / math.sqrt(self.qk_head_dim)
+        if cu_seqlens is not None:
+            # packed documents: attention is causal WITHIN each document
+            # (varlen path; rotary positions must already restart per doc)
+            assert B == 1, "packed cu_seqlens input expects batch dim 1"
+            from ....ops import flash_attn_varlen_func
+
+            attn = flash_attn_varlen_func(
+                q_full.squeeze(0), k_full.squeeze(0).contiguous(),
+                v_in.squeeze(0).contiguous(), cu_seqlens,
+                causal=True, softmax_scale=scale,
+            ).unsqueeze(0)
+        else:
+            attn = flash_attn_func(
+                q_full, k_full.contiguous(), v_in.contiguous(), causal=True,
+                softmax_scale=scale,
+            )
         attn = attn[..., : self.v_head_dim].reshape(B, S, H * self.v_head_dim)
         return self.o_proj(attn)

@@ -6,8 +6,11 @@ optional learnable attention sinks, and LSE output (needed for context-
 parallel ring merging). CPU: eager fp32 oracle with identical semantics
 (reference wrapper: d9d/kernel/flash_attn/function.py).
 
-Layout: q (B, S, Hq, D), k/v (B, S, Hkv, D), out (B, S, Hq, D),
-lse (B, Hq, S) natural-log-sum-exp of the scores row.
+Layout: q (B, S, Hq, Dqk), k (B, S, Hkv, Dqk), v (B, S, Hkv, Dv),
+out (B, S, Hq, Dv), lse (B, Hq, S) natural-log-sum-exp of the scores row.
+GPU head dims: Dqk and Dv up to 128 each (the narrower side is zero-padded to
+the wider), or Dqk up to 192 with Dv up to 128 (the kernels' <192, 128> pair,
+MLA's default shape); anything wider raises ValueError before any launch.
 """
 
 import math
@@ -69,15 +72,58 @@ def _eager_attention(
     return out.permute(0, 2, 1, 3).to(q.dtype), lse
 
 
+#: head dims up to which one padded D serves q, k and v (the kernels' D = D pairs)
+_MAX_SQUARE_HEAD_DIM = 128
+#: the one wide kernel pair: qk head dim up to 192 with v head dim up to 128
+_MAX_WIDE_QK_HEAD_DIM = 192
+_MAX_WIDE_V_HEAD_DIM = 128
+
+
+def head_dim_route(d_qk: int, d_v: int) -> str:
+    """How the GPU path serves a (qk, v) head-dim pair.
+
+    "legacy pad": both dims fit the D = D kernels; the narrower side is
+    zero-padded to the wider one. "wide": q, k, v go to the kernel as they
+    are and it runs the <192, 128> pair. Anything else raises ValueError.
+    """
+    if max(d_qk, d_v) <= _MAX_SQUARE_HEAD_DIM:
+        return "legacy pad"
+    if d_qk <= _MAX_WIDE_QK_HEAD_DIM and d_v <= _MAX_WIDE_V_HEAD_DIM:
+        return "wide"
+    raise ValueError(
+        f"flash attention supports qk head_dim <= {_MAX_WIDE_QK_HEAD_DIM} with "
+        f"v head_dim <= {_MAX_WIDE_V_HEAD_DIM}; got qk {d_qk}, v {d_v}"
+    )
+
+
+def _pad_narrow_side(q, k, v, route: str):
+    """Zero-pad the narrower of qk / v on the "legacy pad" route: zero V
+    columns add nothing to PV, zero q/k columns nothing to the dots. F.pad
+    keeps it differentiable; the caller slices out[..., :Dv]."""
+    Dq, Dv = q.shape[-1], v.shape[-1]
+    if route == "wide" or Dq == Dv:
+        return q, k, v
+    import torch.nn.functional as F
+
+    if Dv < Dq:
+        return q, k, F.pad(v, (0, Dq - Dv))
+    return F.pad(q, (0, Dv - Dq)), F.pad(k, (0, Dv - Dq)), v
+
+
 class _FlashAttnFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, sinks, causal, softmax_scale, window_left, q_offset):
         ext = get_ext()
-        out, lse = ext.flash_attn_fwd(
+        # the <192, 128> kernels return a third tensor, out's bf16 rounding
+        # residual: the backward's delta = rowsum(dout * out) needs it where
+        # the softmax is near one-hot
+        out, lse, *out_lo = ext.flash_attn_fwd(
             q.contiguous(), k.contiguous(), v.contiguous(), sinks, None, None,
             causal, softmax_scale, window_left, q_offset,
         )
-        ctx.save_for_backward(q, k, v, out, lse, *( [sinks] if sinks is not None else [] ))
+        ctx.save_for_backward(q, k, v, out, lse, *out_lo,
+                              *([sinks] if sinks is not None else []))
+        ctx.has_out_lo = bool(out_lo)
         ctx.causal = causal
         ctx.softmax_scale = softmax_scale
         ctx.window_left = window_left
@@ -91,6 +137,7 @@ class _FlashAttnFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, dlse):
         q, k, v, out, lse = ctx.saved_tensors[:5]
+        out_lo = ctx.saved_tensors[5] if ctx.has_out_lo else None
         if dout is None:
             dout = torch.zeros_like(out)
         ext = get_ext()
@@ -103,10 +150,11 @@ class _FlashAttnFunction(torch.autograd.Function):
             dout.contiguous(), q.contiguous(), k.contiguous(), v.contiguous(),
             out.contiguous(), lse, None, None,
             ctx.causal, ctx.softmax_scale, ctx.window_left, ctx.q_offset, dlse,
+            out_lo,
         )
         dsinks = None
         if ctx.has_sinks:
-            sinks = ctx.saved_tensors[5]
+            sinks = ctx.saved_tensors[-1]
             # p_sink(b,h,t) = exp(sink_h - lse);
             # dsink_h = sum p_sink * (dlse - delta)
             # with delta = rowsum(dout * out) (analytic sink grad, reference
@@ -131,35 +179,22 @@ def flash_attn_func(
     return_lse: bool = False,
     q_offset: int = 0,
 ):
-    """Scaled-dot-product attention. q (B,S,Hq,D); k/v (B,S,Hkv,D)."""
+    """Scaled-dot-product attention. q (B,S,Hq,Dqk); k (B,S,Hkv,Dqk);
+    v (B,S,Hkv,Dv); out (B,S,Hq,Dv). On the GPU Dqk and Dv up to 128 each, or
+    Dqk up to 192 with Dv up to 128 (see head_dim_route)."""
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(q.shape[-1])
     right_ok = window_size[1] < 0 or causal  # right window only via causality
     if q.is_cuda and right_ok:
-        Dq, Dv = q.shape[-1], v.shape[-1]
-        if Dv != Dq:
-            # asymmetric head dims (e.g. MLA: qk 24, v 16): zero-pad the
-            # smaller side -- zero V columns add nothing to PV, zero q/k
-            # columns add nothing to the dots -- and slice the output.
-            # F.pad keeps the whole thing differentiable.
-            import torch.nn.functional as F
-
-            if Dv < Dq:
-                v_in = F.pad(v, (0, Dq - Dv))
-                out, lse = _FlashAttnFunction.apply(
-                    q, k, v_in, sinks, causal, softmax_scale, window_size[0], q_offset
-                )
-                out = out[..., :Dv]
-            else:
-                q_in = F.pad(q, (0, Dv - Dq))
-                k_in = F.pad(k, (0, Dv - Dq))
-                out, lse = _FlashAttnFunction.apply(
-                    q_in, k_in, v, sinks, causal, softmax_scale, window_size[0], q_offset
-                )
-        else:
-            out, lse = _FlashAttnFunction.apply(
-                q, k, v, sinks, causal, softmax_scale, window_size[0], q_offset
-            )
+        # asymmetric head dims: small ones (e.g. MLA at qk 24, v 16) pad the
+        # narrower side; past 128 the kernel takes the two dims as they are
+        Dv = v.shape[-1]
+        q_in, k_in, v_in = _pad_narrow_side(q, k, v, head_dim_route(q.shape[-1], Dv))
+        out, lse = _FlashAttnFunction.apply(
+            q_in, k_in, v_in, sinks, causal, softmax_scale, window_size[0], q_offset
+        )
+        if out.shape[-1] != Dv:
+            out = out[..., :Dv]
     else:
         out, lse = _eager_attention(
             q, k, v, causal, softmax_scale, window_size, sinks, q_offset
@@ -190,11 +225,12 @@ class _FlashAttnVarlenFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, cu_q, cu_k, sinks, causal, softmax_scale, window_left):
         ext = get_ext()
-        out, lse = ext.flash_attn_fwd(
+        out, lse, *out_lo = ext.flash_attn_fwd(  # out_lo: see _FlashAttnFunction
             q.contiguous(), k.contiguous(), v.contiguous(), sinks, cu_q, cu_k,
             causal, softmax_scale, window_left, 0,
         )
-        to_save = [q, k, v, out, lse, cu_q, cu_k]
+        to_save = [q, k, v, out, lse, cu_q, cu_k, *out_lo]
+        ctx.has_out_lo = bool(out_lo)
         if sinks is not None:
             to_save.append(sinks)
         ctx.save_for_backward(*to_save)
@@ -210,6 +246,7 @@ class _FlashAttnVarlenFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, dlse):
         q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors[:7]
+        out_lo = ctx.saved_tensors[7] if ctx.has_out_lo else None
         if dout is None:
             dout = torch.zeros_like(out)
         ext = get_ext()
@@ -217,11 +254,11 @@ class _FlashAttnVarlenFunction(torch.autograd.Function):
         dq, dk, dv = ext.flash_attn_bwd(
             dout.contiguous(), q.contiguous(), k.contiguous(), v.contiguous(),
             out.contiguous(), lse, cu_q, cu_k,
-            ctx.causal, ctx.softmax_scale, ctx.window_left, 0, dlse,
+            ctx.causal, ctx.softmax_scale, ctx.window_left, 0, dlse, out_lo,
         )
         dsinks = None
         if ctx.has_sinks:
-            sinks = ctx.saved_tensors[7]
+            sinks = ctx.saved_tensors[-1]
             delta = (out.float() * dout.float()).sum(-1).permute(1, 0)  # (Hq,total)
             if dlse is not None:
                 delta = delta - dlse
@@ -243,20 +280,25 @@ def flash_attn_varlen_func(
     sinks: torch.Tensor | None = None,
     return_lse: bool = False,
 ):
-    """Packed-sequence attention. q (total_q, Hq, D); k/v (total_k, Hkv, D);
-    cu_seqlens (nseq+1,) int32. lse is (Hq, total_q). Causal masking aligns
-    the end of each sequence's q with the end of its kv (flash-attn
-    convention). Reference: d9d/kernel/flash_attn/function.py varlen path."""
+    """Packed-sequence attention. q (total_q, Hq, Dqk); k (total_k, Hkv, Dqk);
+    v (total_k, Hkv, Dv); cu_seqlens (nseq+1,) int32. out is (total_q, Hq, Dv),
+    lse (Hq, total_q). Causal masking aligns the end of each sequence's q with
+    the end of its kv (flash-attn convention). Head dims as flash_attn_func.
+    Reference: d9d/kernel/flash_attn/function.py varlen path."""
     if cu_seqlens_k is None:
         cu_seqlens_k = cu_seqlens_q
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(q.shape[-1])
     right_ok = window_size[1] < 0 or causal
     if q.is_cuda and right_ok:
+        Dv = v.shape[-1]
+        q_in, k_in, v_in = _pad_narrow_side(q, k, v, head_dim_route(q.shape[-1], Dv))
         out, lse = _FlashAttnVarlenFunction.apply(
-            q, k, v, cu_seqlens_q, cu_seqlens_k, sinks, causal, softmax_scale,
-            window_size[0],
+            q_in, k_in, v_in, cu_seqlens_q, cu_seqlens_k, sinks, causal,
+            softmax_scale, window_size[0],
         )
+        if out.shape[-1] != Dv:
+            out = out[..., :Dv]
     else:
         out, lse = _eager_varlen(
             q, k, v, cu_seqlens_q.cpu(), cu_seqlens_k.cpu(), causal,

@@ -58,10 +58,12 @@ def _block_fwd(q, k, v, causal_block: bool, scale: float):
     off-diagonal earlier chunks attend in full.
     """
     if _use_kernel(q):
+        # [:2]: past head dim 128 the kernel also returns out's rounding
+        # residual, which belongs to a chunk's partial out and is not merged
         out, lse = get_ext().flash_attn_fwd(
             q.contiguous(), k.contiguous(), v.contiguous(), None, None, None,
             causal_block, scale, -1, 0,
-        )
+        )[:2]
         return out, lse
     from ..ops.attention import _eager_attention
 
