@@ -16,6 +16,72 @@ v = (torch.randn(B, H, S, D, device="cuda") * 0.5).bfloat16()
 beta = torch.rand(B, H, S, device="cuda")
 g = -torch.rand(B, H, S, device="cuda") * 0.2
 
+# backward leaf stage: gdn_chunk_bwd_leaf (D9D_GDN_BWD_LEAF=1) against the
+# torch stage (=0) in one process. Device events around windows of ITERS
+# calls, the two paths alternating inside every round, so the spread is taken
+# under the same conditions as the medians. `--bwd-leaf` runs only this.
+def bench_bwd_leaf(rounds=9, iters=10):
+    import json, os
+    from d9d_amd.module.block.attention.linear.gated_deltanet import _chunk_gdn_backward
+
+    qf, kf, vf = q.float(), k.float(), v.float()
+    # bf16 values, as the gradient of the op's bf16 output is: the kernels
+    # take dout in bf16, so both paths then see the same numbers
+    do = torch.randn(B, H, S, D, device="cuda").bfloat16().float()
+
+    def run(flag):
+        os.environ["D9D_GDN_BWD_LEAF"] = flag
+        return _chunk_gdn_backward(qf, kf, vf, beta, g, do)
+
+    def window(flag):
+        start = torch.cuda.Event(enable_timing=True)
+        end = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        start.record()
+        for _ in range(iters):
+            run(flag)
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) / iters
+
+    # same inputs, both paths: the results must agree before the times count
+    for name, a, b in zip(("dq", "dk", "dv", "dbeta", "dg"), run("0"), run("1")):
+        print(f"bwd leaf kernel vs torch stage {name}: max abs diff "
+              f"{(a - b).abs().max().item():.3e} (max abs {a.abs().max().item():.3g})")
+    for flag in ("0", "1", "0", "1"):
+        run(flag)
+    times = {"0": [], "1": []}
+    for _ in range(rounds):
+        for flag in times:
+            times[flag].append(window(flag))
+    res = {"shape": [B, H, S, D], "rounds": rounds, "iters": iters}
+    for flag, name in (("0", "torch_stage"), ("1", "leaf_kernel")):
+        ts = times[flag]
+        res[f"bwd_{name}_ms"] = round(statistics.median(ts), 4)
+        res[f"bwd_{name}_min_ms"] = round(min(ts), 4)
+        res[f"bwd_{name}_max_ms"] = round(max(ts), 4)
+        print(f"gdn bwd D9D_GDN_BWD_LEAF={flag} ({name}): median {statistics.median(ts):.3f} ms"
+              f"  min {min(ts):.3f}  max {max(ts):.3f}")
+    os.environ.pop("D9D_GDN_BWD_LEAF")
+
+    # the kernel alone, on the scan kernels' outputs
+    do16 = do.bfloat16()
+    r, s0 = ext.gdn_chunk_fwd(q, k, v, beta, g, False, True, True)
+    drhs, ds0 = ext.gdn_chunk_bwd_scan(q, k, do16, beta, g)
+    run = lambda flag: ext.gdn_chunk_bwd_leaf(q, k, v, do16, beta, g, r, drhs, s0, ds0)
+    run("1")
+    ts = [window("1") for _ in range(rounds)]
+    res["leaf_kernel_alone_ms"] = round(statistics.median(ts), 4)
+    # per chunk: q, k, v, dout bf16 + r, drhs fp32 + s0, ds0 fp32 in; dq, dk, dv fp32 out
+    nbytes = B * H * (S // 64) * (4 * 8192 + 2 * 16384 + 2 * 16384 + 3 * 16384)
+    print(f"gdn_chunk_bwd_leaf alone: median {statistics.median(ts):.3f} ms  min {min(ts):.3f}"
+          f"  max {max(ts):.3f}  ({nbytes / statistics.median(ts) / 1e9:.2f} TB/s of {nbytes / 1e9:.2f} GB)")
+    print(json.dumps(res))
+
+bench_bwd_leaf()
+if "--bwd-leaf" in sys.argv:
+    sys.exit(0)
+
 def bench(fn, name, flops):
     fn(); torch.cuda.synchronize()
     ts = []

@@ -8,6 +8,8 @@ path):
   (a) varlen : cu_seqlens path, one workgroup per (document, head)
   (b) dense  : the dense kernels on (1, H, T), IGNORING boundaries — the
                wrong model, but the cost baseline for the same tokens
+  (a') varlen_torch_leaf : (a) with D9D_GDN_BWD_LEAF=0, the backward's leaf
+               gradients in torch instead of gdn_chunk_bwd_leaf (fwd+bwd only)
   (c) loop   : one dense call per document
 Timed with device events after warm-up; the variants alternate inside every
 round and the rounds repeat, so the spread is measured under the same
@@ -16,6 +18,7 @@ conditions as the medians. Prints a table and one JSON line.
 import argparse
 import json
 import math
+import os
 import pathlib
 import random
 import statistics
@@ -87,6 +90,13 @@ def main() -> None:
         out = chunk_gated_delta_rule(*leaves, cu_seqlens=cu)
         return torch.autograd.grad(out, leaves, do)
 
+    def fb_varlen_torch_leaf():  # the same with the torch leaf-gradient stage
+        os.environ["D9D_GDN_BWD_LEAF"] = "0"
+        try:
+            return fb_varlen()
+        finally:
+            del os.environ["D9D_GDN_BWD_LEAF"]
+
     def fb_dense():
         out = chunk_gated_delta_rule(*leaves)
         return torch.autograd.grad(out, leaves, do)
@@ -112,7 +122,8 @@ def main() -> None:
 
     groups = {
         "fwd": {"varlen": fwd_varlen, "dense": fwd_dense, "loop": fwd_loop},
-        "fwd_bwd": {"varlen": fb_varlen, "dense": fb_dense, "loop": fb_loop},
+        "fwd_bwd": {"varlen": fb_varlen, "varlen_torch_leaf": fb_varlen_torch_leaf,
+                    "dense": fb_dense, "loop": fb_loop},
     }
     result = {
         "heads": H, "tokens": T, "ndocs": len(lens), "chunks": nc,
@@ -135,7 +146,7 @@ def main() -> None:
             result[f"{gname}_{name}_ms"] = round(med, 4)
             result[f"{gname}_{name}_min_ms"] = round(min(ts), 4)
             result[f"{gname}_{name}_max_ms"] = round(max(ts), 4)
-            print(f"{gname:8s} {name:7s} median {med:8.3f} ms   "
+            print(f"{gname:8s} {name:17s} median {med:8.3f} ms   "
                   f"min {min(ts):8.3f}  max {max(ts):8.3f}")
     print(json.dumps(result))
 

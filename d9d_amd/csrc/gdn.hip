@@ -9,12 +9,16 @@
 //    resident in LDS. MFMA bf16 for the chunk GEMMs (KK^T, QK^T, K@S,
 //    Q@S, N@R, K^T@R), fp32 blocked forward-substitution for the
 //    unit-lower triangular solve. Dk = Dv = 64.
-//    (The python wrapper pairs this forward with a recompute-through-the
-//    torch-WY-graph backward; a native bwd kernel is the follow-up.)
-// 3. Packed-document (cu_seqlens) variants of all four entry points: the
+// 3. The hand-derived backward (gated_deltanet.py _chunk_gdn_backward):
+//    gdn_chunk_fwd with aux outputs recomputes R and the chunk entry
+//    states, gdn_chunk_bwd_scan walks the chunks backward with dL/dState
+//    in LDS, and gdn_chunk_bwd_leaf turns both into dq, dk, dv, dbeta, dg,
+//    one workgroup per chunk.
+// 4. Packed-document (cu_seqlens) variants of every entry point: the
 //    same kernel bodies under a VARLEN template flag — one workgroup per
 //    (document, head) from a zero state, conv taps clipped at the
-//    document start. cu_seqlens is validated on the host before launch.
+//    document start; the leaf kernel takes a last-chunk-of-document flag.
+//    cu_seqlens is validated on the host before launch.
 #include "common.h"
 #include "mfma.h"
 
@@ -578,7 +582,7 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_fwd_kernel(
 //   dS        = e^{gc_last} dS + (e^{gc} K)^T @ (-beta drhs)
 //                                + (e^{gc} Q)^T @ dO
 // Outputs drhs (B,H,S,D fp32) and the per-chunk dL/dS0 (B,H,nc,D,D fp32);
-// the non-sequential leaf gradients stay batched torch GEMMs.
+// the non-sequential leaf gradients are gdn_chunk_bwd_leaf_kernel below.
 template <int DVT>
 struct GdnBwdLds {
   float dS[kGdnD][DVT];           // dL/dState fp32 (v slice)
@@ -864,6 +868,518 @@ __global__ __launch_bounds__(256, 1) void gdn_chunk_bwd_scan_kernel(
       }
     }
     __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// chunked gated delta rule backward LEAF GRADIENTS, Dk = Dv = 64
+// ---------------------------------------------------------------------------
+//
+// The non-sequential half of _chunk_gdn_backward: everything after the two
+// scans is local to one chunk, so one workgroup (4 waves) per (b, h, chunk)
+// turns (q, k, v, dO, beta, g, R, drhs, S0, dS1) into dq, dk, dv, dbeta, dg
+// of its 64 rows. dS1 is ds0 of the NEXT chunk, zero for the last chunk of a
+// row (dense) or of a document (`doc_last`, packed layout of whole chunks).
+// With t the row, j the column of the 64x64 chunk matrices (E = e^{gc},
+// w = e^{gc_63 - gc}, ratio = tril0(e^{gc_t - gc_j}), kk = K K^T, qk = Q K^T):
+//   dwK = R dS1^T            dK  = w dwK            dw = rowsum(dwK * K)
+//   dEQ = dO S0^T            dQ  = E dEQ
+//   G   = drhs S0^T          dK += -beta E G        (dEK = -beta G)
+//   dN  = tril0(dO R^T)      dqk = dN ratio
+//   dM  = -tril-1(drhs R^T)  dkk = beta dM ratio
+//   dQ += dqk K              dK += dqk^T Q + dkk K + dkk^T K
+//   dV  = beta drhs
+//   dbeta = rowsum(dM kk ratio) + rowsum(drhs * V) - E rowsum(G * K)
+//   rr  = (dN qk + beta dM kk) ratio
+//   dgc = -w dw + E rowsum(dEQ * Q) - beta E rowsum(G * K)
+//         + rowsum(rr) - colsum(rr);   dgc_63 += <dS1, S0> e^{gc_63} + sum(w dw)
+//   dg  = reverse cumsum of dgc inside the chunk
+// rowsum(drhs * P), P = V - (E K) S0, is taken as rowsum(drhs * V) -
+// E rowsum(G * K): the same sum reassociated through G, so the (E K) S0
+// product and a transposed image of S0 are never needed.
+//
+// Work split: wave w owns rows 16w..16w+15 of every product. Its A fragments
+// (rows of R, dO, drhs, Q) come straight from global memory: each element
+// is read by exactly one lane. B operands are shared by the four waves and
+// staged once into LDS: K rows, K^T and Q^T images, and two hi/lo image
+// pairs that are reused in phases (`a`: R -> dqk -> dkk; `b`: dS1 -> S0 ->
+// dqk^T -> dkk^T), which keeps the workgroup at ~66 KB, two per CU. kk, qk,
+// ratio, dN and dM live in accumulator registers only.
+//
+// Rounding: q, k, v, dO are bf16 inputs. Every fp32 operand of a product
+// (R, drhs, S0, dS1, dqk, dkk) goes to the MFMA as a bf16 pair hi = bf16(x),
+// lo = bf16(x - hi) with all hi/lo cross terms accumulated in fp32, i.e. it
+// is truncated to ~16 significant bits (2^-17 relative) at the point where
+// it is staged or written to an image; nothing is rounded once to bf16.
+// All sums, decay factors and elementwise math are fp32.
+constexpr int kLeafP = kGdnD + 8;   // LDS row pitch: 144 B rows spread the
+                                    // 16 B fragment reads over the banks
+typedef bf16_t LeafTile[kGdnC][kLeafP];
+
+struct GdnLeafLds {
+  LeafTile kc;                    // K rows        (B of kk, qk; A of kk)
+  LeafTile kT;                    // K^T: kT[d][t] (B of . K; K in C layout)
+  LeafTile qT;                    // Q^T: qT[d][t] (B of . Q; Q in C layout)
+  LeafTile a[2];                  // hi/lo: R, then dqk, then dkk
+  LeafTile b[2];                  // hi/lo: dS1, then S0, then dqk^T, dkk^T
+  float gc[kGdnC];
+  float beta[kGdnC];
+  float dgc[kGdnC];               // row-owned part of dgc
+  float db[kGdnC];                // C-layout part of dbeta
+  float dbv[kGdnC];               // rowsum(drhs * V)
+  float colsum[4][kGdnC];         // per-wave colsum(rr)
+  float red[4];                   // per-wave part of the dgc_63 scalar
+};
+
+// The leaf kernel is built without packed fp32 VALU ops (target attribute
+// below), and only force-inlined code follows a kernel's target: barrier and
+// lane exchange are spelled with the builtins here.
+D9D_DEVICE void leaf_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// value of `x` in lane `src` (taken mod 64) of this wave
+D9D_DEVICE float leaf_shfl(float x, int src) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, x)));
+}
+
+D9D_DEVICE void leaf_split(float x, bf16_t& hi, bf16_t& lo) {
+  hi = (bf16_t)x;
+  lo = (bf16_t)(x - (float)hi);
+}
+
+D9D_DEVICE void leaf_load8(const float* __restrict__ p, float (&x)[8]) {
+  const float4 x0 = *reinterpret_cast<const float4*>(p);
+  const float4 x1 = *reinterpret_cast<const float4*>(p + 4);
+  x[0] = x0.x; x[1] = x0.y; x[2] = x0.z; x[3] = x0.w;
+  x[4] = x1.x; x[5] = x1.y; x[6] = x1.z; x[7] = x1.w;
+}
+
+D9D_DEVICE void leaf_split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    bf16_t h, l;
+    leaf_split(x[j], h, l);
+    hi[j] = h;
+    lo[j] = l;
+  }
+}
+
+// acc (this wave's 16 x 64 band) += A . B^T-image: A fragments a[ks2][image]
+// (NA = 2: hi/lo), B rows b[image][n][k] (NB = 2: hi/lo). Cross terms run
+// smallest first.
+template <int NA, int NB>
+D9D_DEVICE void leaf_mma(f32x4 (&acc)[4], const bf16x8 (&a)[2][NA],
+                         const LeafTile* b, int lane) {
+#pragma unroll
+  for (int ks2 = 0; ks2 < 2; ++ks2) {
+    const int d0 = ks2 * 32 + (lane >> 4) * 8;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int brow = nt * 16 + (lane & 15);
+#pragma unroll
+      for (int ib = NB - 1; ib >= 0; --ib) {
+        const bf16x8 bf = *reinterpret_cast<const bf16x8*>(&b[ib][brow][d0]);
+#pragma unroll
+        for (int ia = NA - 1; ia >= 0; --ia) {
+          acc[nt] = mfma16(a[ks2][ia], bf, acc[nt]);
+        }
+      }
+    }
+  }
+}
+
+// hi/lo A fragments of row `arow` of an LDS image pair
+D9D_DEVICE void leaf_afrag(bf16x8 (&a)[2][2], const LeafTile* img, int arow,
+                           int lane) {
+#pragma unroll
+  for (int ks2 = 0; ks2 < 2; ++ks2) {
+    const int d0 = ks2 * 32 + (lane >> 4) * 8;
+    a[ks2][0] = *reinterpret_cast<const bf16x8*>(&img[0][arow][d0]);
+    a[ks2][1] = *reinterpret_cast<const bf16x8*>(&img[1][arow][d0]);
+  }
+}
+
+// This wave's band of a C-layout fp32 tile -> hi/lo images img[t][j] and
+// imgT[j][t] (a lane's four rows are one 8-byte store of the transpose).
+D9D_DEVICE void leaf_put(const f32x4 (&x)[4], LeafTile* img, LeafTile* imgT,
+                         int tq, int lane) {
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    const int j = nt * 16 + (lane & 15);
+    bf16x4 h4, l4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      bf16_t h, l;
+      leaf_split(x[nt][r], h, l);
+      img[0][tq + r][j] = h;
+      img[1][tq + r][j] = l;
+      h4[r] = h;
+      l4[r] = l;
+    }
+    *reinterpret_cast<bf16x4*>(&imgT[0][j][tq]) = h4;
+    *reinterpret_cast<bf16x4*>(&imgT[1][j][tq]) = l4;
+  }
+}
+
+// (built without packed fp32 VALU ops: plain v_mul / v_fma only)
+__global__ __launch_bounds__(256, 2)
+__attribute__((target("no-packed-fp32-ops"))) void gdn_chunk_bwd_leaf_kernel(
+    const bf16_t* __restrict__ q,    // (B, H, Sp, D), Sp = 64 nc
+    const bf16_t* __restrict__ k,
+    const bf16_t* __restrict__ v,
+    const bf16_t* __restrict__ dout,
+    const float* __restrict__ beta,       // (B, H, Sp)
+    const float* __restrict__ decay_log,  // (B, H, Sp)
+    const float* __restrict__ r_in,       // (B, H, Sp, D)  gdn_chunk_fwd aux
+    const float* __restrict__ drhs,       // (B, H, Sp, D)  reverse scan
+    const float* __restrict__ s0,         // (B, H, nc, D, D)
+    const float* __restrict__ ds0,        // (B, H, nc, D, D)
+    float* __restrict__ dq,               // (B, H, Sp, D)
+    float* __restrict__ dk,
+    float* __restrict__ dv,
+    float* __restrict__ dbeta,            // (B, H, Sp)
+    float* __restrict__ dg,
+    const int* __restrict__ doc_last,     // (nc,) packed rows only, or nullptr
+    int64_t n_chunks, int64_t nc) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  GdnLeafLds& L = *reinterpret_cast<GdnLeafLds*>(smem_raw);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int lr = lane & 15;
+  const int lq = lane >> 4;
+  const int64_t chunk = blockIdx.x;
+  if (chunk >= n_chunks) return;
+  const int64_t c = chunk % nc;
+  // the last chunk of a row / document hands its state to nobody: dS1 = 0
+  // (and ds0[chunk + 1] is never addressed past the end of a row)
+  const bool last = (c == nc - 1) || (doc_last != nullptr && doc_last[c] != 0);
+  const int64_t row0 = chunk * kGdnC;
+  const int64_t tile0 = row0 * kGdnD;
+  const float* s0p = s0 + chunk * (int64_t)(kGdnD * kGdnD);
+  const float* ds1p = ds0 + (chunk + 1) * (int64_t)(kGdnD * kGdnD);
+
+  // ---- stage: decay scan, K / K^T / Q^T, R and dS1 images; S0 to registers
+  if (wave == 0) {
+    float run = decay_log[row0 + lane];
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float up = leaf_shfl(run, lane - off);
+      if (lane >= off) run += up;
+    }
+    L.gc[lane] = run;
+    L.beta[lane] = beta[row0 + lane];
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int i = tid + u * 256;
+    const int row = i >> 3;
+    const int col = (i & 7) * 8;
+    const bf16x8 kv =
+        *reinterpret_cast<const bf16x8*>(k + tile0 + row * kGdnD + col);
+    const bf16x8 qv =
+        *reinterpret_cast<const bf16x8*>(q + tile0 + row * kGdnD + col);
+    *reinterpret_cast<bf16x8*>(&L.kc[row][col]) = kv;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      L.kT[col + j][row] = kv[j];
+      L.qT[col + j][row] = qv[j];
+    }
+  }
+  float4 s0r[4];
+  float frob = 0.f;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = tid + u * 256;
+    const int row = i >> 4;
+    const int col = (i & 15) * 4;
+    const float4 rv = *reinterpret_cast<const float4*>(
+        r_in + tile0 + row * kGdnD + col);
+    const float rx[4] = {rv.x, rv.y, rv.z, rv.w};
+    bf16x4 h4, l4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      bf16_t h, l;
+      leaf_split(rx[j], h, l);
+      h4[j] = h;
+      l4[j] = l;
+    }
+    *reinterpret_cast<bf16x4*>(&L.a[0][row][col]) = h4;
+    *reinterpret_cast<bf16x4*>(&L.a[1][row][col]) = l4;
+    s0r[u] = *reinterpret_cast<const float4*>(s0p + row * kGdnD + col);
+    if (!last) {
+      const float4 dv4 =
+          *reinterpret_cast<const float4*>(ds1p + row * kGdnD + col);
+      const float dx[4] = {dv4.x, dv4.y, dv4.z, dv4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        bf16_t h, l;
+        leaf_split(dx[j], h, l);
+        h4[j] = h;
+        l4[j] = l;
+      }
+      *reinterpret_cast<bf16x4*>(&L.b[0][row][col]) = h4;
+      *reinterpret_cast<bf16x4*>(&L.b[1][row][col]) = l4;
+      frob += dv4.x * s0r[u].x + dv4.y * s0r[u].y + dv4.z * s0r[u].z +
+              dv4.w * s0r[u].w;
+    }
+  }
+  leaf_barrier();
+
+  // this lane's rows in the C layout: tq .. tq+3; A fragments: row arow
+  const int tq = wave * 16 + lq * 4;
+  const int arow = wave * 16 + lr;
+  const int64_t aoff = tile0 + arow * kGdnD + lq * 8;   // + ks2 * 32
+  const float g_end = L.gc[kGdnC - 1];
+  const float e_end = expf(g_end);
+  float gct[4], et[4], wt[4], bt[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    gct[r] = L.gc[tq + r];
+    et[r] = expf(gct[r]);
+    wt[r] = expf(g_end - gct[r]);
+    bt[r] = L.beta[tq + r];
+  }
+
+  f32x4 dqa[4], dka[4];
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    dqa[nt] = {0.f, 0.f, 0.f, 0.f};
+    dka[nt] = {0.f, 0.f, 0.f, 0.f};
+  }
+  float rowacc[4] = {0.f, 0.f, 0.f, 0.f};   // dgc partial of rows tq..tq+3
+  float dbacc[4] = {0.f, 0.f, 0.f, 0.f};    // dbeta partial of the same rows
+  float tot = frob * e_end;                 // dgc_63 scalar partial
+
+  // ---- dwK = R dS1^T: dK = w dwK, dw = rowsum(dwK * K) -------------------
+  if (!last) {
+    bf16x8 ar[2][2];
+#pragma unroll
+    for (int ks2 = 0; ks2 < 2; ++ks2) {
+      float x[8];
+      leaf_load8(r_in + aoff + ks2 * 32, x);
+      leaf_split8(x, ar[ks2][0], ar[ks2][1]);
+    }
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    leaf_mma<2, 2>(acc, ar, L.b, lane);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const bf16x4 kf =
+          *reinterpret_cast<const bf16x4*>(&L.kT[nt * 16 + lr][tq]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float dkw = acc[nt][r] * wt[r];
+        dka[nt][r] = dkw;
+        const float p = dkw * (float)kf[r];
+        rowacc[r] -= p;
+        tot += p;
+      }
+    }
+  }
+  leaf_barrier();   // dS1 image consumed: S0 takes its place
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = tid + u * 256;
+    const int row = i >> 4;
+    const int col = (i & 15) * 4;
+    const float sx[4] = {s0r[u].x, s0r[u].y, s0r[u].z, s0r[u].w};
+    bf16x4 h4, l4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      bf16_t h, l;
+      leaf_split(sx[j], h, l);
+      h4[j] = h;
+      l4[j] = l;
+    }
+    *reinterpret_cast<bf16x4*>(&L.b[0][row][col]) = h4;
+    *reinterpret_cast<bf16x4*>(&L.b[1][row][col]) = l4;
+  }
+
+  // A fragments of dO and drhs (kept for the R^T products); on the way
+  // dV = beta drhs and rowsum(drhs * V) for dbeta
+  bf16x8 ado[2][1], adr[2][2];
+  {
+    const float ba = L.beta[arow];
+    float dot = 0.f;
+#pragma unroll
+    for (int ks2 = 0; ks2 < 2; ++ks2) {
+      const int64_t off = aoff + ks2 * 32;
+      ado[ks2][0] = *reinterpret_cast<const bf16x8*>(dout + off);
+      const bf16x8 vv = *reinterpret_cast<const bf16x8*>(v + off);
+      float x[8];
+      leaf_load8(drhs + off, x);
+      leaf_split8(x, adr[ks2][0], adr[ks2][1]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dot += x[j] * (float)vv[j];
+      *reinterpret_cast<f32x4*>(dv + off) =
+          f32x4{ba * x[0], ba * x[1], ba * x[2], ba * x[3]};
+      *reinterpret_cast<f32x4*>(dv + off + 4) =
+          f32x4{ba * x[4], ba * x[5], ba * x[6], ba * x[7]};
+    }
+    dot += leaf_shfl(dot, lane ^ 16);
+    dot += leaf_shfl(dot, lane ^ 32);
+    if (lq == 0) L.dbv[arow] = dot;
+  }
+  leaf_barrier();
+
+  // ---- dEQ = dO S0^T: dQ = E dEQ, dgc += E rowsum(dEQ * Q) ---------------
+  {
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    leaf_mma<1, 2>(acc, ado, L.b, lane);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const bf16x4 qf =
+          *reinterpret_cast<const bf16x4*>(&L.qT[nt * 16 + lr][tq]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = acc[nt][r] * et[r];
+        dqa[nt][r] = e;
+        rowacc[r] += e * (float)qf[r];
+      }
+    }
+  }
+  // ---- G = drhs S0^T: dK -= beta E G, dgc -= beta E rowsum(G * K),
+  //      dbeta -= E rowsum(G * K) -----------------------------------------
+  {
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    leaf_mma<2, 2>(acc, adr, L.b, lane);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const bf16x4 kf =
+          *reinterpret_cast<const bf16x4*>(&L.kT[nt * 16 + lr][tq]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float ge = acc[nt][r] * et[r];
+        const float gk = ge * (float)kf[r];
+        dka[nt][r] -= bt[r] * ge;
+        rowacc[r] -= bt[r] * gk;
+        dbacc[r] -= gk;
+      }
+    }
+  }
+
+  // ---- dN, dM, kk, qk in registers -> dqk (x), dkk (y), dbeta, rr sums ---
+  f32x4 x[4], y[4];
+  {
+    f32x4 an[4], am[4], akk[4], aqk[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      an[nt] = {0.f, 0.f, 0.f, 0.f};
+      am[nt] = {0.f, 0.f, 0.f, 0.f};
+      akk[nt] = {0.f, 0.f, 0.f, 0.f};
+      aqk[nt] = {0.f, 0.f, 0.f, 0.f};
+    }
+    bf16x8 ak[2][1], aq[2][1];
+#pragma unroll
+    for (int ks2 = 0; ks2 < 2; ++ks2) {
+      ak[ks2][0] =
+          *reinterpret_cast<const bf16x8*>(&L.kc[arow][ks2 * 32 + lq * 8]);
+      aq[ks2][0] = *reinterpret_cast<const bf16x8*>(q + aoff + ks2 * 32);
+    }
+    leaf_mma<1, 2>(an, ado, L.a, lane);
+    leaf_mma<2, 2>(am, adr, L.a, lane);
+    leaf_mma<1, 1>(akk, ak, &L.kc, lane);
+    leaf_mma<1, 1>(aqk, aq, &L.kc, lane);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int j = nt * 16 + lr;
+      const float gcj = L.gc[j];
+      float colacc = 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = tq + r;
+        // decay ratio only where t >= j, so it stays <= 1
+        const float ratio = (j <= t) ? expf(gct[r] - gcj) : 0.f;
+        const float dn = (j <= t) ? an[nt][r] : 0.f;
+        const float dm = (j < t) ? -am[nt][r] : 0.f;
+        const float dkkr = dm * bt[r];
+        dbacc[r] += dm * akk[nt][r] * ratio;
+        const float rr = (dn * aqk[nt][r] + dkkr * akk[nt][r]) * ratio;
+        rowacc[r] += rr;
+        colacc += rr;
+        x[nt][r] = dn * ratio;
+        y[nt][r] = dkkr * ratio;
+      }
+      colacc += leaf_shfl(colacc, lane ^ 16);
+      colacc += leaf_shfl(colacc, lane ^ 32);
+      if (lq == 0) L.colsum[wave][j] = colacc;
+    }
+  }
+  leaf_barrier();   // R and S0 images consumed
+
+  // ---- dQ += dqk K, dK += dqk^T Q ----------------------------------------
+  leaf_put(x, L.a, L.b, tq, lane);
+  leaf_barrier();
+  {
+    bf16x8 af[2][2];
+    leaf_afrag(af, L.a, arow, lane);
+    leaf_mma<2, 1>(dqa, af, &L.kT, lane);
+    leaf_afrag(af, L.b, arow, lane);
+    leaf_mma<2, 1>(dka, af, &L.qT, lane);
+  }
+  leaf_barrier();
+
+  // ---- dK += dkk K + dkk^T K ---------------------------------------------
+  leaf_put(y, L.a, L.b, tq, lane);
+  leaf_barrier();
+  {
+    bf16x8 af[2][2];
+    leaf_afrag(af, L.a, arow, lane);
+    leaf_mma<2, 1>(dka, af, &L.kT, lane);
+    leaf_afrag(af, L.b, arow, lane);
+    leaf_mma<2, 1>(dka, af, &L.kT, lane);
+  }
+
+  // ---- outputs -----------------------------------------------------------
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t off = tile0 + (tq + r) * kGdnD + nt * 16 + lr;
+      dq[off] = dqa[nt][r];
+      dk[off] = dka[nt][r];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+      rowacc[r] += leaf_shfl(rowacc[r], lane ^ off);
+      dbacc[r] += leaf_shfl(dbacc[r], lane ^ off);
+    }
+    if (lr == 0) {
+      L.dgc[tq + r] = rowacc[r];
+      L.db[tq + r] = dbacc[r];
+    }
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) tot += leaf_shfl(tot, lane ^ off);
+  if (lane == 0) L.red[wave] = tot;
+  leaf_barrier();
+  if (wave == 0) {
+    const int t = lane;
+    float dgc = L.dgc[t] - (L.colsum[0][t] + L.colsum[1][t] +
+                            L.colsum[2][t] + L.colsum[3][t]);
+    if (t == kGdnC - 1) dgc += L.red[0] + L.red[1] + L.red[2] + L.red[3];
+    // gc = cumsum(g): dg_t = sum of dgc over the rows t .. 63 of the chunk
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float dn = leaf_shfl(dgc, lane + off);
+      if (lane + off < 64) dgc += dn;
+    }
+    dg[row0 + t] = dgc;
+    dbeta[row0 + t] = L.db[t] + L.dbv[t];
   }
 }
 
@@ -1196,6 +1712,119 @@ std::vector<torch::Tensor> gdn_chunk_bwd_scan_varlen(
                             docs.chunk_off_dev.data_ptr<int>(), (int)H,
                             docs.nc);
   return {drhs, ds0};
+}
+
+namespace {
+
+// Leaf-gradient stage shared by the dense and packed entry points: checks
+// the four scan products against q's (B, H, Sp, 64), allocates the five
+// outputs and launches one workgroup per chunk. `doc_last` is the (nc,)
+// int32 last-chunk-of-a-document flag on the device, or undefined (dense).
+std::vector<torch::Tensor> gdn_bwd_leaf_impl(
+    const char* who, const torch::Tensor& q, const torch::Tensor& k,
+    const torch::Tensor& v, const torch::Tensor& dout,
+    const torch::Tensor& beta, const torch::Tensor& decay_log,
+    const torch::Tensor& r, const torch::Tensor& drhs,
+    const torch::Tensor& s0, const torch::Tensor& ds0,
+    const torch::Tensor& doc_last) {
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2);
+  const int64_t nc = S / 64;
+  TORCH_CHECK(dout.is_cuda() && dout.scalar_type() == torch::kBFloat16 &&
+                  dout.sizes() == q.sizes(),
+              who, ": dout must be a bf16 device tensor shaped like q");
+  for (const torch::Tensor* t : {&r, &drhs}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
+                    t->is_contiguous() && t->sizes() == q.sizes(),
+                who, ": r and drhs must be contiguous fp32 (B, H, S, 64)");
+  }
+  for (const torch::Tensor* t : {&s0, &ds0}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
+                    t->is_contiguous() && t->dim() == 5 && t->size(0) == B &&
+                    t->size(1) == H && t->size(2) == nc &&
+                    t->size(3) == 64 && t->size(4) == 64,
+                who, ": s0 and ds0 must be contiguous fp32 (B, H, S / 64, 64, 64)");
+  }
+  auto qc = q.contiguous();
+  auto kc = k.contiguous();
+  auto vc = v.contiguous();
+  auto dc = dout.contiguous();
+  auto bc = beta.to(torch::kFloat32).contiguous();
+  auto gc = decay_log.to(torch::kFloat32).contiguous();
+  auto f32 = torch::dtype(torch::kFloat32).device(q.device());
+  auto dq = torch::empty({B, H, S, 64}, f32);
+  auto dk = torch::empty({B, H, S, 64}, f32);
+  auto dv = torch::empty({B, H, S, 64}, f32);
+  auto dbeta = torch::empty({B, H, S}, f32);
+  auto dg = torch::empty({B, H, S}, f32);
+  const int64_t n_chunks = B * H * nc;
+  if (n_chunks == 0) return {dq, dk, dv, dbeta, dg};
+  TORCH_CHECK(n_chunks < (int64_t)1 << 31, who, ": too many chunks for one grid");
+
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&d9d::gdn_chunk_bwd_leaf_kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)sizeof(d9d::GdnLeafLds));
+    attr_set = true;
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(d9d::gdn_chunk_bwd_leaf_kernel, dim3((unsigned)n_chunks),
+                     dim3(256), sizeof(d9d::GdnLeafLds), stream,
+                     reinterpret_cast<const __bf16*>(qc.data_ptr()),
+                     reinterpret_cast<const __bf16*>(kc.data_ptr()),
+                     reinterpret_cast<const __bf16*>(vc.data_ptr()),
+                     reinterpret_cast<const __bf16*>(dc.data_ptr()),
+                     bc.data_ptr<float>(), gc.data_ptr<float>(),
+                     r.data_ptr<float>(), drhs.data_ptr<float>(),
+                     s0.data_ptr<float>(), ds0.data_ptr<float>(),
+                     dq.data_ptr<float>(), dk.data_ptr<float>(),
+                     dv.data_ptr<float>(), dbeta.data_ptr<float>(),
+                     dg.data_ptr<float>(),
+                     doc_last.defined() ? doc_last.data_ptr<int>() : nullptr,
+                     n_chunks, nc);
+  return {dq, dk, dv, dbeta, dg};
+}
+
+}  // namespace
+
+// Per-chunk leaf gradients of the hand-derived backward: (dq, dk, dv) fp32
+// (B, H, S, 64) and (dbeta, dg) fp32 (B, H, S) from the forward aux (r, s0)
+// and the reverse scan's (drhs, ds0). S must be a multiple of 64.
+std::vector<torch::Tensor> gdn_chunk_bwd_leaf(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
+    torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
+    torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0) {
+  gdn_dense_checks("gdn_chunk_bwd_leaf", q, k, v, beta, decay_log);
+  TORCH_CHECK(q.size(2) % 64 == 0,
+              "gdn_chunk_bwd_leaf: S must be a multiple of 64, got ", q.size(2));
+  return gdn_bwd_leaf_impl("gdn_chunk_bwd_leaf", q, k, v, dout, beta,
+                           decay_log, r, drhs, s0, ds0, torch::Tensor());
+}
+
+// Packed documents in the chunk-aligned layout the backward gathers into:
+// every cu_seqlens entry is a multiple of 64, and the last chunk of each
+// document takes dS1 = 0 instead of the next document's ds0.
+std::vector<torch::Tensor> gdn_chunk_bwd_leaf_varlen(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
+    torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
+    torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0,
+    torch::Tensor cu_seqlens) {
+  gdn_varlen_checks(q, k, v, beta, decay_log);
+  const int64_t T = q.size(2);
+  auto docs = gdn_check_docs(cu_seqlens, q.size(0), T, q.device(),
+                             /*with_chunks=*/false);
+  auto cu_cpu = cu_seqlens.cpu().contiguous();
+  const int* cu = cu_cpu.data_ptr<int>();
+  auto last = torch::zeros({T / 64}, torch::dtype(torch::kInt32));
+  int* lp = last.data_ptr<int>();
+  for (int64_t i = 0; i <= docs.nseq; ++i) {
+    TORCH_CHECK(cu[i] % 64 == 0, "gdn_chunk_bwd_leaf_varlen: cu_seqlens[", i,
+                "] = ", cu[i], " is not a multiple of 64");
+    if (i > 0 && cu[i] > cu[i - 1]) lp[cu[i] / 64 - 1] = 1;
+  }
+  return gdn_bwd_leaf_impl("gdn_chunk_bwd_leaf_varlen", q, k, v, dout, beta,
+                           decay_log, r, drhs, s0, ds0, last.to(q.device()));
 }
 
 namespace {

@@ -183,9 +183,10 @@ def chunk_gated_delta_rule(
 ) -> torch.Tensor:
     """GPU (Dk = Dv = 64): fused CDNA4 chunk kernel (csrc/gdn.hip) — the
     fp32 state stays LDS-resident across the chunk loop and every chunk
-    GEMM lands on MFMA; backward recomputes through the torch WY graph
-    (a native bwd kernel is the follow-up). Other shapes / CPU: the
-    chunked-parallel WY torch path below.
+    GEMM lands on MFMA; the hand-derived backward runs on three more
+    kernels there (aux forward, reverse scan, per-chunk leaf gradients)
+    when S is a multiple of 64. Other shapes / CPU: the chunked-parallel
+    WY torch path below.
 
     `cu_seqlens` ((nseq+1,) int32, either device) marks packed documents
     along S: the state is zero at each document start and no gradient
@@ -347,6 +348,86 @@ def _chunk_gated_delta_rule_torch(
     return torch.cat(outs, dim=2).to(v.dtype)
 
 
+def _gdn_chunk_prologue(Qc, Kc, gc):
+    """Per-chunk decay factors and 64x64 matrices shared by the torch scans
+    and the torch leaf stage: (E, Eend, w, ratio, kk, qk)."""
+    E = gc.exp()                                  # (B,H,nc,C)
+    g_tot = gc[..., -1:]                          # (B,H,nc,1)
+    Eend = g_tot.exp()
+    w = (g_tot - gc).exp()                        # Eend / E
+    ratio = torch.exp(gc.unsqueeze(-1) - gc.unsqueeze(-2)).tril(0)
+    kk = torch.matmul(Kc, Kc.transpose(-1, -2))
+    qk = torch.matmul(Qc, Kc.transpose(-1, -2))
+    return E, Eend, w, ratio, kk, qk
+
+
+def _gdn_leaf_grads_torch(Qc, Kc, Vc, dOc, bc, gc, Rs, drhss, S0s, dS1s,
+                          pro=None):
+    """Batched per-chunk leaf gradients of `_chunk_gdn_backward` in torch
+    (any float dtype): chunked Q, K (B,H,nc,C,Dk), V, dO, R, drhs
+    (B,H,nc,C,Dv), beta and gc = cumsum(g) (B,H,nc,C), chunk entry states S0
+    and per-chunk dL/dS1 (B,H,nc,Dk,Dv); `pro` is `_gdn_chunk_prologue` where
+    the caller already has it. Returns chunked (dQ, dK, dV, dbeta, dg). The
+    specification of csrc/gdn.hip's gdn_chunk_bwd_leaf kernel."""
+    if pro is None:
+        pro = _gdn_chunk_prologue(Qc, Kc, gc)
+    E, Eend, w, ratio, kk, qk = pro
+    EK = E.unsqueeze(-1) * Kc
+
+    # ---- batched leaf gradients --------------------------------------------
+    dgc = torch.zeros_like(gc)
+
+    # S1 = Eend S0 + (w*K)^T R
+    dwK = torch.matmul(Rs, dS1s.transpose(-1, -2))           # (B,H,nc,C,Dk)
+    dK = dwK * w.unsqueeze(-1)
+    dw = (dwK * Kc).sum(-1)                                  # (B,H,nc,C)
+    dg_tot = (dS1s * S0s).sum((-1, -2)) * Eend.squeeze(-1)   # (B,H,nc)
+    dg_tot = dg_tot + (dw * w).sum(-1)
+    dgc = dgc - dw * w
+    dgc[..., -1] += dg_tot
+    # NOTE: dR from this path entered the scan already (wK dS term)
+
+    # O = (E*Q) S0 + N R
+    dEQ = torch.matmul(dOc, S0s.transpose(-1, -2))           # (B,H,nc,C,Dk)
+    dQ = dEQ * E.unsqueeze(-1)
+    dgc = dgc + (dEQ * Qc).sum(-1) * E
+    dN = torch.matmul(dOc, Rs.transpose(-1, -2)).tril(0)
+    # (dR's N^T dO term entered the scan)
+
+    # N = tril0(QK^T * ratio)
+    dqk = dN * ratio
+    dQ = dQ + torch.matmul(dqk, Kc)
+    dK = dK + torch.matmul(dqk.transpose(-1, -2), Qc)
+    dratio = dN * qk
+
+    # R = A^{-1} rhs: dA = -drhs R^T (restricted to M's strictly-lower part)
+    dM = -torch.matmul(drhss, Rs.transpose(-1, -2)).tril(-1)
+    # M = tril_{-1}(b_row KK^T ratio)
+    db = (dM * kk * ratio).sum(-1)
+    dkkr = dM * bc.unsqueeze(-1)
+    dkk = dkkr * ratio
+    dK = dK + torch.matmul(dkk, Kc) + torch.matmul(dkk.transpose(-1, -2), Kc)
+    dratio = dratio + dkkr * kk
+
+    # ratio_tj = exp(gc_t - gc_j), masked t >= j
+    rr = dratio * ratio
+    dgc = dgc + rr.sum(-1) - rr.sum(-2)
+
+    # rhs = b_row * P, P = V - (E*K) S0
+    P = Vc - torch.matmul(EK, S0s)
+    db = db + (drhss * P).sum(-1)
+    dT_all = -(bc.unsqueeze(-1) * drhss)
+    dV = bc.unsqueeze(-1) * drhss
+    dEK = torch.matmul(dT_all, S0s.transpose(-1, -2))
+    dK = dK + dEK * E.unsqueeze(-1)
+    dgc = dgc + (dEK * Kc).sum(-1) * E
+    # (dS0 contributions entered the scan)
+
+    # gc = cumsum(g): dg_t = sum_{tau >= t} dgc_tau  (within the chunk)
+    dg = dgc.flip(-1).cumsum(-1).flip(-1)
+    return dQ, dK, dV, db, dg
+
+
 def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
                         cu_seqlens=None):
     """Explicit backward of `_chunk_gated_delta_rule_torch` (same WY chunk
@@ -433,29 +514,23 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
     Vc = v32.view(B, H, nc, C, Dv)
     dOc = do32.view(B, H, nc, C, Dv)
     bc = b32.view(B, H, nc, C)
-    gc = g32.view(B, H, nc, C).cumsum(dim=-1)
-    E = gc.exp()                                  # (B,H,nc,C)
-    g_tot = gc[..., -1:]                          # (B,H,nc,1)
-    Eend = g_tot.exp()
-    w = (g_tot - gc).exp()                        # Eend / E
 
-    ratio = torch.exp(gc.unsqueeze(-1) - gc.unsqueeze(-2)).tril(0)
-    kk = torch.matmul(Kc, Kc.transpose(-1, -2))
-    qk = torch.matmul(Qc, Kc.transpose(-1, -2))
-
-    EK = E.unsqueeze(-1) * Kc
-    EQ = E.unsqueeze(-1) * Qc
-    wK = w.unsqueeze(-1) * Kc
-
-    # ---- the two sequential scans: CDNA4 kernels when they apply, else
-    # torch loops (the scans are 92% of the backward at bench shape —
-    # profiles/gdn_kernels.md)
+    # ---- the two sequential scans and the per-chunk leaf gradients: CDNA4
+    # kernels when they apply, else torch (profiles/gdn_kernels.md)
     import os
 
     use_scan_kernels = (
         _use_gdn_kernels(q) and Dk == 64 and Dv == 64 and C == 64 and pad == 0
         and os.environ.get("D9D_GDN_BWD_SCAN", "1") != "0"
     )
+    use_leaf_kernel = (
+        use_scan_kernels and os.environ.get("D9D_GDN_BWD_LEAF", "1") != "0"
+    )
+    # the kernels recompute the decay scan and the 64x64 chunk matrices
+    # themselves: gc and the prologue exist only for the torch stages
+    gc = pro = None
+    if not use_leaf_kernel:
+        gc = g32.view(B, H, nc, C).cumsum(dim=-1)
     if use_scan_kernels:
         ext = get_ext()
         q16 = q32.to(torch.bfloat16).contiguous()
@@ -472,6 +547,13 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
             drhs_flat, dS0s = ext.gdn_chunk_bwd_scan_varlen(
                 q16, k16, do16, b32.contiguous(), g32.contiguous(), cu_lay,
             )
+            if use_leaf_kernel:
+                # dS1 = the next chunk's dS0, zero at each document's last
+                # chunk: the kernel reads cu_lay, no shifted copy is made
+                leaf = ext.gdn_chunk_bwd_leaf_varlen(
+                    q16, k16, v16, do16, b32.contiguous(), g32.contiguous(),
+                    r_flat, drhs_flat, S0s, dS0s, cu_lay,
+                )
         else:
             r_flat, S0s = ext.gdn_chunk_fwd(
                 q16, k16, v16, b32.contiguous(), g32.contiguous(),
@@ -480,9 +562,19 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
             drhs_flat, dS0s = ext.gdn_chunk_bwd_scan(
                 q16, k16, do16, b32.contiguous(), g32.contiguous(),
             )
+            if use_leaf_kernel:
+                leaf = ext.gdn_chunk_bwd_leaf(
+                    q16, k16, v16, do16, b32.contiguous(), g32.contiguous(),
+                    r_flat, drhs_flat, S0s, dS0s,
+                )
         Rs = r_flat.view(B, H, nc, C, Dv)
         drhss = drhs_flat.view(B, H, nc, C, Dv)
     else:
+        pro = _gdn_chunk_prologue(Qc, Kc, gc)
+        E, Eend, w, ratio, kk, qk = pro
+        EK = E.unsqueeze(-1) * Kc
+        EQ = E.unsqueeze(-1) * Qc
+        wK = w.unsqueeze(-1) * Kc
         M = (bc.unsqueeze(-1) * kk * ratio).tril(-1)
         eye = torch.eye(C, dtype=torch.float32, device=q.device)
         A = M + eye
@@ -528,64 +620,19 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
             dS0s[:, :, i] = dS0  # dL/dS0 of THIS chunk == dS1 of the previous
             dS = dS0
 
-    dS1s = torch.cat(
-        [dS0s[:, :, 1:], torch.zeros_like(dS0s[:, :, :1])], dim=2
-    )  # per-chunk dL/d(S1)
-    if varlen:
-        # a document's last chunk hands its state to nobody
-        dS1s[:, :, doc_last.to(q.device)] = 0.0
-
-    # ---- batched leaf gradients --------------------------------------------
-    dgc = torch.zeros_like(gc)
-
-    # S1 = Eend S0 + (w*K)^T R
-    dwK = torch.matmul(Rs, dS1s.transpose(-1, -2))           # (B,H,nc,C,Dk)
-    dK = dwK * w.unsqueeze(-1)
-    dw = (dwK * Kc).sum(-1)                                  # (B,H,nc,C)
-    dg_tot = (dS1s * S0s).sum((-1, -2)) * Eend.squeeze(-1)   # (B,H,nc)
-    dg_tot = dg_tot + (dw * w).sum(-1)
-    dgc = dgc - dw * w
-    dgc[..., -1] += dg_tot
-    # NOTE: dR from this path entered the scan already (wK dS term)
-
-    # O = (E*Q) S0 + N R
-    dEQ = torch.matmul(dOc, S0s.transpose(-1, -2))           # (B,H,nc,C,Dk)
-    dQ = dEQ * E.unsqueeze(-1)
-    dgc = dgc + (dEQ * Qc).sum(-1) * E
-    dN = torch.matmul(dOc, Rs.transpose(-1, -2)).tril(0)
-    # (dR's N^T dO term entered the scan)
-
-    # N = tril0(QK^T * ratio)
-    dqk = dN * ratio
-    dQ = dQ + torch.matmul(dqk, Kc)
-    dK = dK + torch.matmul(dqk.transpose(-1, -2), Qc)
-    dratio = dN * qk
-
-    # R = A^{-1} rhs: dA = -drhs R^T (restricted to M's strictly-lower part)
-    dM = -torch.matmul(drhss, Rs.transpose(-1, -2)).tril(-1)
-    # M = tril_{-1}(b_row KK^T ratio)
-    db = (dM * kk * ratio).sum(-1)
-    dkkr = dM * bc.unsqueeze(-1)
-    dkk = dkkr * ratio
-    dK = dK + torch.matmul(dkk, Kc) + torch.matmul(dkk.transpose(-1, -2), Kc)
-    dratio = dratio + dkkr * kk
-
-    # ratio_tj = exp(gc_t - gc_j), masked t >= j
-    rr = dratio * ratio
-    dgc = dgc + rr.sum(-1) - rr.sum(-2)
-
-    # rhs = b_row * P, P = V - (E*K) S0
-    P = Vc - torch.matmul(EK, S0s)
-    db = db + (drhss * P).sum(-1)
-    dT_all = -(bc.unsqueeze(-1) * drhss)
-    dV = bc.unsqueeze(-1) * drhss
-    dEK = torch.matmul(dT_all, S0s.transpose(-1, -2))
-    dK = dK + dEK * E.unsqueeze(-1)
-    dgc = dgc + (dEK * Kc).sum(-1) * E
-    # (dS0 contributions entered the scan)
-
-    # gc = cumsum(g): dg_t = sum_{tau >= t} dgc_tau  (within the chunk)
-    dg = dgc.flip(-1).cumsum(-1).flip(-1)
+    if use_leaf_kernel:
+        dQ, dK, dV = (t.view(B, H, nc, C, -1) for t in leaf[:3])
+        db, dg = (t.view(B, H, nc, C) for t in leaf[3:])
+    else:
+        dS1s = torch.cat(
+            [dS0s[:, :, 1:], torch.zeros_like(dS0s[:, :, :1])], dim=2
+        )  # per-chunk dL/d(S1)
+        if varlen:
+            # a document's last chunk hands its state to nobody
+            dS1s[:, :, doc_last.to(q.device)] = 0.0
+        dQ, dK, dV, db, dg = _gdn_leaf_grads_torch(
+            Qc, Kc, Vc, dOc, bc, gc, Rs, drhss, S0s, dS1s, pro
+        )
 
     def to_rows(t):  # (B, H, nc, C, ...) -> the caller's (B, H, S, ...) rows
         t = t.reshape(B, H, Sp, *t.shape[4:])
