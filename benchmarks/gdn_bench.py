@@ -9,7 +9,11 @@ from d9d_amd.module.block.attention.linear.gated_deltanet import (
 
 ext = get_ext()
 torch.manual_seed(0)
-B, H, S, D = 8, 16, 4096, 64
+# --head-dim 128: the wide chunk kernels (forward, aux, reverse scan) against
+# the torch path; everything below bench_wide() is the D = 64 report
+D = int(sys.argv[sys.argv.index("--head-dim") + 1]) if "--head-dim" in sys.argv else 64
+assert D in (64, 128), "--head-dim takes 64 or 128"
+B, H, S = 8, 16, 4096
 q = F.normalize(torch.randn(B, H, S, D, device="cuda"), dim=-1).bfloat16()
 k = F.normalize(torch.randn(B, H, S, D, device="cuda"), dim=-1).bfloat16()
 v = (torch.randn(B, H, S, D, device="cuda") * 0.5).bfloat16()
@@ -77,6 +81,69 @@ def bench_bwd_leaf(rounds=9, iters=10):
     print(f"gdn_chunk_bwd_leaf alone: median {statistics.median(ts):.3f} ms  min {min(ts):.3f}"
           f"  max {max(ts):.3f}  ({nbytes / statistics.median(ts) / 1e9:.2f} TB/s of {nbytes / 1e9:.2f} GB)")
     print(json.dumps(res))
+
+# head dim 128: the op on the chunk kernels (forward; aux forward + reverse
+# scan + torch leaf stage in the backward) against the torch path it took
+# before they existed (torch WY forward, D9D_GDN_BWD_SCAN=0 backward). Device
+# events around windows of ITERS calls, the two paths alternating inside
+# every round.
+def bench_wide(rounds=7, iters=4):
+    import json, os
+    from d9d_amd.module.block.attention.linear.gated_deltanet import (
+        _GdnChunkFunction, chunk_gated_delta_rule,
+    )
+
+    do = torch.randn(B, H, S, D, device="cuda").bfloat16()
+
+    def fwd(kernel):
+        with torch.no_grad():
+            if kernel:
+                return chunk_gated_delta_rule(q, k, v, beta, g)
+            return _chunk_gated_delta_rule_torch(q, k, v, beta, g)
+
+    def fwd_bwd(kernel):
+        os.environ["D9D_GDN_BWD_SCAN"] = "1" if kernel else "0"
+        leaves = [t.detach().requires_grad_(True) for t in (q, k, v, beta, g)]
+        out = _GdnChunkFunction.apply(*leaves, 64, kernel, None)
+        out.backward(do)
+        return [out.detach()] + [t.grad for t in leaves]
+
+    def window(fn, kernel):
+        start = torch.cuda.Event(enable_timing=True)
+        end = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        start.record()
+        for _ in range(iters):
+            fn(kernel)
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) / iters
+
+    # same inputs, both paths: the results must agree before the times count
+    for name, a, b in zip(("out", "dq", "dk", "dv", "dbeta", "dg"), fwd_bwd(False), fwd_bwd(True)):
+        print(f"kernel vs torch path {name}: max abs diff "
+              f"{(a.float() - b.float()).abs().max().item():.3e} (max abs {a.float().abs().max().item():.3g})")
+    res = {"shape": [B, H, S, D], "rounds": rounds, "iters": iters}
+    for what, fn in (("fwd", fwd), ("fwd_bwd", fwd_bwd)):
+        for kernel in (False, True, False, True):
+            fn(kernel)
+        times = {False: [], True: []}
+        for _ in range(rounds):
+            for kernel in times:
+                times[kernel].append(window(fn, kernel))
+        for kernel, name in ((False, "torch"), (True, "kernel")):
+            ts = times[kernel]
+            res[f"{what}_{name}_ms"] = round(statistics.median(ts), 4)
+            res[f"{what}_{name}_min_ms"] = round(min(ts), 4)
+            res[f"{what}_{name}_max_ms"] = round(max(ts), 4)
+            print(f"gdn D={D} {what} ({name} path): median {statistics.median(ts):.3f} ms"
+                  f"  min {min(ts):.3f}  max {max(ts):.3f}")
+    os.environ.pop("D9D_GDN_BWD_SCAN")
+    print(json.dumps(res))
+
+if D == 128:
+    bench_wide()
+    sys.exit(0)
 
 bench_bwd_leaf()
 if "--bwd-leaf" in sys.argv:

@@ -19,6 +19,9 @@
 //    (document, head) from a zero state, conv taps clipped at the
 //    document start; the leaf kernel takes a last-chunk-of-document flag.
 //    cu_seqlens is validated on the host before launch.
+// 5. Dk = Dv = 128 variants of the forward (with its aux outputs) and the
+//    reverse scan, dense and packed: 8-wave workgroups with the fp32 state
+//    in registers (the `wide` section below). The leaf kernel is D = 64 only.
 #include "common.h"
 #include "mfma.h"
 
@@ -1383,6 +1386,606 @@ __attribute__((target("no-packed-fp32-ops"))) void gdn_chunk_bwd_leaf_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// chunked gated delta rule at Dk = Dv = 128: forward (+ aux) and reverse scan
+// ---------------------------------------------------------------------------
+//
+// The same per-chunk algebra and the same rounding points as the D = 64
+// kernels above (state before K@S and Q@S, e^{gc} K, e^{gc} Q, N, R before
+// N@R, K e^{gc_last - gc}, the output), laid out for twice the head width:
+//
+//   * Dv split: gridDim.y = 128 / DVT column slices of the state per head,
+//     DVT = 64 (two slices) or 32 (four). The K-side work (KK^T, QK^T, the
+//     decay scan, M, N) is repeated per slice, so four slices are only taken
+//     while all of them still sit on the chip at once (launcher below).
+//   * 8 waves per workgroup. Wave w = (rs = w & 3, nh = w >> 2) owns rows
+//     16 rs .. 16 rs + 15 of every chunk product and half nh of its columns:
+//     2 of the 4 column tiles of M and N, DVT / 32 of the v tiles, each with
+//     4 contraction steps over Dk = 128. The VALU phases (staging, scaling,
+//     the fp32 state update, the 128 x DVT fp32 stores) run 512 wide.
+//   * The fp32 state (dL/dState in the reverse scan) lives in REGISTERS, not
+//     LDS: thread (dkg, dvq) keeps the DVT/16 x 4 block at rows
+//     dkg * DVT/16, columns 4 dvq, for the whole chunk loop. The rank-64
+//     update reads one 16 B row piece of R and one 4-8 B piece of the scaled
+//     K per chunk row for 8-16 FMAs; the bf16 transposed image for the next
+//     chunk's MFMAs, s0 / ds0 and the final state are written from the
+//     registers. This frees 32 KB of LDS, which pays for
+//   * padded rows (+16 B) on every bf16 tile, so the 16 B fragment reads of
+//     16 consecutive rows spread over the banks (a 256 B row pitch would put
+//     them all on one), and two scaled-K scratch tiles instead of one, so a
+//     chunk takes 6 barriers instead of 9;
+//   * the triangular solves run in place (rhs -> R, dR -> drhs) with the
+//     D = 64 scheme: wave owns DVT / 8 columns, lanes split j in 64 / (DVT/8)
+//     groups, xor-shuffle combine.
+//   * the decay scan is a 64-lane shuffle scan by one wave.
+// LDS: forward 145 KB (DVT 64) / 120 KB (DVT 32), reverse scan the same;
+// one workgroup per CU either way.
+constexpr int kGdnW = 128;            // Dk = Dv
+constexpr int kGdnWP = kGdnW + 8;     // row pitch of a Dk-wide bf16 tile
+constexpr int kGdnCP = kGdnC + 8;     // row pitch of a chunk-wide bf16 tile
+constexpr int kGdnWT = 512;           // threads per workgroup
+constexpr int kGdnLdsMax = 160 * 1024;
+typedef bf16_t WideTile[kGdnC][kGdnWP];
+
+template <int DVT>
+struct GdnWideLds {
+  float M[kGdnC][kGdnC + 1];      // solve matrix (+1 pad)
+  float R[kGdnC][DVT + 4];        // rhs, solved in place to R
+  WideTile kc;                    // K chunk
+  WideTile qc;                    // Q chunk
+  WideTile ek;                    // e^{gc} K, then e^{gc} Q
+  WideTile wk;                    // K e^{gc_last - gc}
+  bf16_t vc[kGdnC][DVT];          // V chunk slice
+  bf16_t sbT[DVT][kGdnWP];        // state^T cast to bf16: sbT[v][k]
+  bf16_t nb[kGdnC][kGdnCP];       // N cast to bf16
+  bf16_t rbT[DVT][kGdnCP];        // R^T cast to bf16: rbT[v][t]
+  float gc[kGdnC];
+  float beta[kGdnC];
+};
+
+template <int DVT>
+struct GdnWideBwdLds {
+  float M[kGdnC][kGdnC + 1];      // solve matrix (+1 pad)
+  float dx[kGdnC][DVT + 4];       // dR, solved in place to drhs
+  WideTile kc;                    // K chunk
+  WideTile qc;                    // Q chunk
+  WideTile wq;                    // K e^{gc_last - gc}, then e^{gc} Q
+  WideTile ek;                    // e^{gc} K
+  bf16_t doc[kGdnC][DVT];         // dO chunk slice
+  bf16_t doT[DVT][kGdnCP];        // dO^T (B fragments of N^T @ dO)
+  bf16_t dsT[DVT][kGdnWP];        // dS^T cast to bf16 (B fragments)
+  bf16_t nbT[kGdnC][kGdnCP];      // N^T cast to bf16 (A fragments)
+  float gc[kGdnC];
+  float beta[kGdnC];
+};
+
+static_assert(sizeof(GdnWideLds<64>) <= kGdnLdsMax &&
+                  sizeof(GdnWideLds<32>) <= kGdnLdsMax &&
+                  sizeof(GdnWideBwdLds<64>) <= kGdnLdsMax &&
+                  sizeof(GdnWideBwdLds<32>) <= kGdnLdsMax,
+              "a workgroup has 160 KB of LDS");
+
+// Rows [0, c_rows) of a (rows, 128) bf16 matrix into a padded tile, zeros in
+// the rows past the end.
+D9D_DEVICE void wide_stage(WideTile& dst, const bf16_t* __restrict__ src,
+                           int c_rows) {
+  for (int i = threadIdx.x; i < kGdnC * kGdnW / 8; i += kGdnWT) {
+    const int row = i / (kGdnW / 8);
+    const int col = (i % (kGdnW / 8)) * 8;
+    bf16x8 x = {};
+    if (row < c_rows) {
+      x = *reinterpret_cast<const bf16x8*>(src + (int64_t)row * kGdnW + col);
+    }
+    *reinterpret_cast<bf16x8*>(&dst[row][col]) = x;
+  }
+}
+
+// dst[row][:] = bf16(src[row][:] * sc(row)), sc = e^{gc_row}, or with TAIL
+// e^{g_tot - gc_row} inside the chunk and 0 past its end
+template <bool TAIL>
+D9D_DEVICE void wide_scale(WideTile& dst, const WideTile& src, const float* gc,
+                           float g_tot, int c_rows) {
+  for (int i = threadIdx.x; i < kGdnC * kGdnW / 8; i += kGdnWT) {
+    const int row = i / (kGdnW / 8);
+    const int col = (i % (kGdnW / 8)) * 8;
+    float sc = __builtin_amdgcn_exp2f((TAIL ? g_tot - gc[row] : gc[row]) *
+                                      1.44269504f);
+    if (TAIL && row >= c_rows) sc = 0.f;
+    const bf16x8 x = *reinterpret_cast<const bf16x8*>(&src[row][col]);
+    bf16x8 y;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = (bf16_t)((float)x[j] * sc);
+    *reinterpret_cast<bf16x8*>(&dst[row][col]) = y;
+  }
+}
+
+// gc = cumsum(g) (constant past the end) and beta (zero past the end) of
+// one chunk, by ONE whole wave: lane t owns row t.
+D9D_DEVICE void wide_gates(const float* __restrict__ gp,
+                           const float* __restrict__ bp, int c_rows,
+                           float* gc, float* beta) {
+  const int t = threadIdx.x & 63;
+  float run = (t < c_rows) ? gp[t] : 0.f;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float up = leaf_shfl(run, t - off);
+    if (t >= off) run += up;
+  }
+  gc[t] = run;
+  beta[t] = (t < c_rows) ? bp[t] : 0.f;
+}
+
+// acc[nt] += A[arow][0 : 32 KS] . B[brow0 + 16 nt + (lane & 15)][0 : 32 KS]
+template <int NT, int KS, int PA, int PB>
+D9D_DEVICE void wide_mma(f32x4 (&acc)[NT], bf16_t (*a)[PA], int arow,
+                         bf16_t (*b)[PB], int brow0, int lane) {
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int d0 = ks * 32 + (lane >> 4) * 8;
+    const bf16x8 af = *reinterpret_cast<const bf16x8*>(&a[arow][d0]);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int brow = brow0 + nt * 16 + (lane & 15);
+      const bf16x8 bf = *reinterpret_cast<const bf16x8*>(&b[brow][d0]);
+      acc[nt] = mfma16(af, bf, acc[nt]);
+    }
+  }
+}
+
+// bf16 transposed image of this thread's TK x 4 block of the fp32 state:
+// img[dv0 + b][dk0 + a] = bf16(st[a][b])
+template <int TK>
+D9D_DEVICE void wide_state_image(bf16_t (*img)[kGdnWP], const float (&st)[TK][4],
+                                 int dk0, int dv0) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+#pragma unroll
+    for (int a = 0; a < TK; ++a) img[dv0 + b][dk0 + a] = (bf16_t)st[a][b];
+  }
+}
+
+// rows dk0 .. dk0 + TK of a (128, 128) fp32 matrix, columns col .. col + 3
+template <int TK>
+D9D_DEVICE void wide_state_store(float* __restrict__ dst, const float (&st)[TK][4],
+                                 int dk0, int col) {
+#pragma unroll
+  for (int a = 0; a < TK; ++a) {
+    *reinterpret_cast<float4*>(dst + (int64_t)(dk0 + a) * kGdnW + col) =
+        make_float4(st[a][0], st[a][1], st[a][2], st[a][3]);
+  }
+}
+
+// (built without packed fp32 VALU ops, like the leaf kernel)
+template <int DVT, bool VARLEN>
+__global__ __launch_bounds__(kGdnWT, 1)
+__attribute__((target("no-packed-fp32-ops"))) void gdn_chunk_fwd_wide_kernel(
+    const bf16_t* __restrict__ q,   // (B, H, S, 128)
+    const bf16_t* __restrict__ k,
+    const bf16_t* __restrict__ v,
+    const float* __restrict__ beta,      // (B, H, S)
+    const float* __restrict__ decay_log, // (B, H, S)
+    bf16_t* __restrict__ out,            // (B, H, S, 128) or nullptr
+    float* __restrict__ final_state,     // (n_wg, 128, 128) or nullptr
+    float* __restrict__ r_out,           // (B, H, S, 128) fp32 or nullptr
+    float* __restrict__ s0_out,          // (B, H, nc, 128, 128) fp32 or nullptr
+    int64_t n_wg, int64_t S,
+    const int* __restrict__ cu,          // varlen only (see GdnSpan)
+    const int* __restrict__ chunk_off,   // varlen only
+    int H, int64_t nc_total) {           // varlen only
+  constexpr int NTV = DVT / 32;        // v tiles per wave
+  constexpr int TK = DVT / 16;         // state rows per thread
+  constexpr int NV4 = DVT / 4;         // 4-column groups of the slice
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  GdnWideLds<DVT>& L = *reinterpret_cast<GdnWideLds<DVT>*>(smem_raw);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int rs = wave & 3;             // row strip
+  const int nh = wave >> 2;            // column half
+  const int arow = rs * 16 + (lane & 15);        // A fragment row
+  const int crow = rs * 16 + (lane >> 4) * 4;    // first C layout row
+  const int ccol = lane & 15;                    // C layout column in a tile
+  const int dk0 = (tid / NV4) * TK;    // this thread's state block
+  const int dv0 = (tid % NV4) * 4;
+  const int64_t bh = blockIdx.x;
+  const int v0 = blockIdx.y * DVT;     // this block's Dv slice
+  if (bh >= n_wg) return;
+
+  const GdnSpan span = gdn_span<VARLEN>(bh, S, cu, chunk_off, H, nc_total);
+  const int64_t len = span.len;
+  const bf16_t* qp = q + span.row0 * kGdnW;
+  const bf16_t* kp = k + span.row0 * kGdnW;
+  const bf16_t* vp = v + span.row0 * kGdnW + v0;
+  const float* bp = beta + span.row0;
+  const float* gp = decay_log + span.row0;
+
+  float st[TK][4];
+#pragma unroll
+  for (int a = 0; a < TK; ++a) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) st[a][b] = 0.f;
+  }
+
+  const float kLog2eG = 1.44269504f;
+  const int n_chunks = (int)((len + kGdnC - 1) / kGdnC);
+  for (int ch = 0; ch < n_chunks; ++ch) {
+    const int s0 = ch * kGdnC;
+    const int c_rows = min((int)(len - (int64_t)s0), kGdnC);
+
+    // ---- stage chunk tiles (zero-pad past c_rows), state^T bf16, gates ---
+    wide_stage(L.kc, kp + (int64_t)s0 * kGdnW, c_rows);
+    wide_stage(L.qc, qp + (int64_t)s0 * kGdnW, c_rows);
+    for (int i = tid; i < kGdnC * DVT / 8; i += kGdnWT) {
+      const int row = i / (DVT / 8);
+      const int col = (i % (DVT / 8)) * 8;
+      bf16x8 x = {};
+      if (row < c_rows) {
+        x = *reinterpret_cast<const bf16x8*>(
+            vp + (int64_t)(s0 + row) * kGdnW + col);
+      }
+      *reinterpret_cast<bf16x8*>(&L.vc[row][col]) = x;
+    }
+    wide_state_image<TK>(L.sbT, st, dk0, dv0);
+    if (wave == 0) wide_gates(gp + s0, bp + s0, c_rows, L.gc, L.beta);
+    if (s0_out != nullptr) {
+      wide_state_store<TK>(
+          s0_out + (span.chunk0 + ch) * (int64_t)kGdnW * kGdnW, st, dk0,
+          v0 + dv0);
+    }
+    leaf_barrier();
+
+    // ---- M = tril(beta * KK^T * ratio, -1); e^{gc} K and w K scratch -----
+    const float g_tot = L.gc[c_rows - 1];
+    {
+      f32x4 acc[2];
+      acc[0] = acc[1] = {0.f, 0.f, 0.f, 0.f};
+      wide_mma<2, 4>(acc, L.kc, arow, L.kc, nh * 32, lane);
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int t = crow + r;
+          const int j = nh * 32 + nt * 16 + ccol;
+          float m = 0.f;
+          if (j < t) {
+            m = L.beta[t] * acc[nt][r] *
+                __builtin_amdgcn_exp2f((L.gc[t] - L.gc[j]) * kLog2eG);
+          }
+          L.M[t][j] = m;
+        }
+      }
+    }
+    wide_scale<false>(L.ek, L.kc, L.gc, g_tot, c_rows);
+    wide_scale<true>(L.wk, L.kc, L.gc, g_tot, c_rows);
+    leaf_barrier();
+
+    // ---- rhs = diag(beta) (V - (e^{gc} K) @ S) ---------------------------
+    {
+      f32x4 acc[NTV];
+#pragma unroll
+      for (int nt = 0; nt < NTV; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+      wide_mma<NTV, 4>(acc, L.ek, arow, L.sbT, nh * (DVT / 2), lane);
+#pragma unroll
+      for (int nt = 0; nt < NTV; ++nt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int t = crow + r;
+          const int vcol = nh * (DVT / 2) + nt * 16 + ccol;
+          L.R[t][vcol] = L.beta[t] * ((float)L.vc[t][vcol] - acc[nt][r]);
+        }
+      }
+    }
+    leaf_barrier();
+
+    // ---- forward substitution: (I + M) R = rhs, in place -----------------
+    // wave w owns Dv columns [w CPW, (w+1) CPW); lane = qj * CPW + c: each
+    // lane partial-sums its j-group of M[t,:] * R[:,col], xor-shuffles
+    // combine the JG partials and the qj == 0 lane writes R[t][col] (+ the
+    // bf16 R^T copy). DVT 64: 8 cols x 8 groups; DVT 32: 4 cols x 16.
+    {
+      constexpr int CPW = DVT / 8;
+      constexpr int JG = 64 / CPW;
+      constexpr int jspan = kGdnC / JG;
+      const int qj = lane / CPW;
+      const int col = wave * CPW + lane % CPW;
+      for (int t = 0; t < kGdnC; ++t) {
+        float part = 0.f;
+        const int jend = min(t, (qj + 1) * jspan);
+        for (int j = qj * jspan; j < jend; ++j) {
+          part += L.M[t][j] * L.R[j][col];
+        }
+        // all 64 lanes active and convergent
+#pragma unroll
+        for (int off = CPW; off < 64; off <<= 1) {
+          part += leaf_shfl(part, lane ^ off);
+        }
+        const float r_t = L.R[t][col] - part;
+        if (qj == 0) {
+          L.R[t][col] = r_t;
+          L.rbT[col][t] = (bf16_t)r_t;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    leaf_barrier();
+
+    if (r_out != nullptr) {
+      for (int i = tid; i < kGdnC * NV4; i += kGdnWT) {
+        const int t = i / NV4;
+        const int c4 = (i % NV4) * 4;
+        if (t < c_rows) {
+          *reinterpret_cast<float4*>(
+              r_out + (span.row0 + s0 + t) * kGdnW + v0 + c4) =
+              *reinterpret_cast<const float4*>(&L.R[t][c4]);
+        }
+      }
+    }
+
+    // ---- N (bf16) and O = (e^{gc} Q) @ S + N @ R -------------------------
+    // (skipped when out == nullptr: the backward recompute only needs the
+    // solve results and chunk states)
+    if (out != nullptr) {
+      wide_scale<false>(L.ek, L.qc, L.gc, g_tot, c_rows);
+      {
+        f32x4 acc[2];
+        acc[0] = acc[1] = {0.f, 0.f, 0.f, 0.f};
+        wide_mma<2, 4>(acc, L.qc, arow, L.kc, nh * 32, lane);
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int t = crow + r;
+            const int j = nh * 32 + nt * 16 + ccol;
+            float n = 0.f;
+            if (j <= t) {
+              n = acc[nt][r] *
+                  __builtin_amdgcn_exp2f((L.gc[t] - L.gc[j]) * kLog2eG);
+            }
+            L.nb[t][j] = (bf16_t)n;
+          }
+        }
+      }
+      leaf_barrier();
+      f32x4 acc[NTV];
+#pragma unroll
+      for (int nt = 0; nt < NTV; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+      wide_mma<NTV, 4>(acc, L.ek, arow, L.sbT, nh * (DVT / 2), lane);
+      wide_mma<NTV, 2>(acc, L.nb, arow, L.rbT, nh * (DVT / 2), lane);
+      bf16_t* op = out + (span.row0 + s0) * kGdnW + v0;
+#pragma unroll
+      for (int nt = 0; nt < NTV; ++nt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int t = crow + r;
+          const int vcol = nh * (DVT / 2) + nt * 16 + ccol;
+          if (t < c_rows) op[(int64_t)t * kGdnW + vcol] = (bf16_t)acc[nt][r];
+        }
+      }
+    }
+
+    // ---- state = e^{gc_last} S + (K e^{gc_last - gc})^T @ R, in registers
+    {
+      const float e_tot = __builtin_amdgcn_exp2f(g_tot * kLog2eG);
+#pragma unroll
+      for (int a = 0; a < TK; ++a) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) st[a][b] *= e_tot;
+      }
+      for (int t = 0; t < c_rows; ++t) {
+        const float4 rv = *reinterpret_cast<const float4*>(&L.R[t][dv0]);
+        const float r4[4] = {rv.x, rv.y, rv.z, rv.w};
+#pragma unroll
+        for (int a = 0; a < TK; ++a) {
+          const float kv = (float)L.wk[t][dk0 + a];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) st[a][b] += kv * r4[b];
+        }
+      }
+    }
+    leaf_barrier();
+  }
+
+  if (final_state != nullptr) {
+    wide_state_store<TK>(final_state + bh * kGdnW * kGdnW, st, dk0, v0 + dv0);
+  }
+}
+
+// Reverse scan at D = 128: the algebra of gdn_chunk_bwd_scan_kernel in the
+// layout of the forward kernel above, dL/dState in registers.
+template <int DVT, bool VARLEN>
+__global__ __launch_bounds__(kGdnWT, 1)
+__attribute__((target("no-packed-fp32-ops"))) void gdn_chunk_bwd_scan_wide_kernel(
+    const bf16_t* __restrict__ q,    // (B, H, S, 128)
+    const bf16_t* __restrict__ k,
+    const bf16_t* __restrict__ dout, // (B, H, S, 128)
+    const float* __restrict__ beta,
+    const float* __restrict__ decay_log,
+    float* __restrict__ drhs_out,    // (B, H, S, 128)
+    float* __restrict__ ds0_out,     // (B, H, nc, 128, 128)
+    int64_t n_wg, int64_t S,
+    const int* __restrict__ cu,          // varlen only (see GdnSpan)
+    const int* __restrict__ chunk_off,   // varlen only
+    int H, int64_t nc_total) {           // varlen only
+  constexpr int NTV = DVT / 32;
+  constexpr int TK = DVT / 16;
+  constexpr int NV4 = DVT / 4;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  GdnWideBwdLds<DVT>& L = *reinterpret_cast<GdnWideBwdLds<DVT>*>(smem_raw);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int rs = wave & 3;
+  const int nh = wave >> 2;
+  const int arow = rs * 16 + (lane & 15);
+  const int crow = rs * 16 + (lane >> 4) * 4;
+  const int ccol = lane & 15;
+  const int dk0 = (tid / NV4) * TK;
+  const int dv0 = (tid % NV4) * 4;
+  const int64_t bh = blockIdx.x;
+  const int v0 = blockIdx.y * DVT;
+  if (bh >= n_wg) return;
+
+  const GdnSpan span = gdn_span<VARLEN>(bh, S, cu, chunk_off, H, nc_total);
+  const int64_t len = span.len;
+  const bf16_t* qp = q + span.row0 * kGdnW;
+  const bf16_t* kp = k + span.row0 * kGdnW;
+  const bf16_t* dop = dout + span.row0 * kGdnW + v0;
+  const float* bp = beta + span.row0;
+  const float* gp = decay_log + span.row0;
+
+  float dS[TK][4];
+#pragma unroll
+  for (int a = 0; a < TK; ++a) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) dS[a][b] = 0.f;
+  }
+
+  const float kLog2eG = 1.44269504f;
+  const int n_chunks = (int)((len + kGdnC - 1) / kGdnC);
+  for (int ch = n_chunks - 1; ch >= 0; --ch) {
+    const int s0 = ch * kGdnC;
+    const int c_rows = min((int)(len - (int64_t)s0), kGdnC);
+
+    // ---- stage chunk tiles (zero-pad), dO and dO^T, dS^T, gates ----------
+    wide_stage(L.kc, kp + (int64_t)s0 * kGdnW, c_rows);
+    wide_stage(L.qc, qp + (int64_t)s0 * kGdnW, c_rows);
+    for (int i = tid; i < kGdnC * DVT / 8; i += kGdnWT) {
+      const int row = i / (DVT / 8);
+      const int col = (i % (DVT / 8)) * 8;
+      bf16x8 x = {};
+      if (row < c_rows) {
+        x = *reinterpret_cast<const bf16x8*>(
+            dop + (int64_t)(s0 + row) * kGdnW + col);
+      }
+      *reinterpret_cast<bf16x8*>(&L.doc[row][col]) = x;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) L.doT[col + j][row] = x[j];
+    }
+    wide_state_image<TK>(L.dsT, dS, dk0, dv0);
+    if (wave == 0) wide_gates(gp + s0, bp + s0, c_rows, L.gc, L.beta);
+    leaf_barrier();
+
+    // ---- M (fp32, solve matrix), N^T (bf16), w K and e^{gc} K ------------
+    const float g_tot = L.gc[c_rows - 1];
+    {
+      f32x4 accm[2], accn[2];
+      accm[0] = accm[1] = accn[0] = accn[1] = {0.f, 0.f, 0.f, 0.f};
+      wide_mma<2, 4>(accm, L.kc, arow, L.kc, nh * 32, lane);
+      wide_mma<2, 4>(accn, L.qc, arow, L.kc, nh * 32, lane);
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int t = crow + r;
+          const int j = nh * 32 + nt * 16 + ccol;
+          const float ratio =
+              __builtin_amdgcn_exp2f((L.gc[t] - L.gc[j]) * kLog2eG);
+          L.M[t][j] = (j < t) ? L.beta[t] * accm[nt][r] * ratio : 0.f;
+          L.nbT[j][t] = (bf16_t)((j <= t) ? accn[nt][r] * ratio : 0.f);
+        }
+      }
+    }
+    wide_scale<true>(L.wq, L.kc, L.gc, g_tot, c_rows);
+    wide_scale<false>(L.ek, L.kc, L.gc, g_tot, c_rows);
+    leaf_barrier();
+
+    // ---- dR = wK @ dS + N^T @ dO  (fp32 into L.dx) -----------------------
+    {
+      f32x4 acc[NTV];
+#pragma unroll
+      for (int nt = 0; nt < NTV; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+      wide_mma<NTV, 4>(acc, L.wq, arow, L.dsT, nh * (DVT / 2), lane);
+      wide_mma<NTV, 2>(acc, L.nbT, arow, L.doT, nh * (DVT / 2), lane);
+#pragma unroll
+      for (int nt = 0; nt < NTV; ++nt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          L.dx[crow + r][nh * (DVT / 2) + nt * 16 + ccol] = acc[nt][r];
+        }
+      }
+    }
+    leaf_barrier();
+
+    // ---- backward substitution: (I + M)^T drhs = dR, in place ------------
+    // drhs[t] = dR[t] - sum_{j > t} M[j][t] * drhs[j]; the forward solve's
+    // column / j-group split, t walked downward.
+    {
+      constexpr int CPW = DVT / 8;
+      constexpr int JG = 64 / CPW;
+      constexpr int jspan = kGdnC / JG;
+      const int qj = lane / CPW;
+      const int col = wave * CPW + lane % CPW;
+      for (int t = kGdnC - 2; t >= 0; --t) {
+        float part = 0.f;
+        const int jlo = max(t + 1, qj * jspan);
+        const int jhi = (qj + 1) * jspan;
+        for (int j = jlo; j < jhi; ++j) {
+          part += L.M[j][t] * L.dx[j][col];
+        }
+#pragma unroll
+        for (int off = CPW; off < 64; off <<= 1) {
+          part += leaf_shfl(part, lane ^ off);
+        }
+        if (qj == 0) {
+          L.dx[t][col] -= part;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    leaf_barrier();
+
+    // drhs out (fp32)
+    for (int i = tid; i < kGdnC * NV4; i += kGdnWT) {
+      const int t = i / NV4;
+      const int c4 = (i % NV4) * 4;
+      if (t < c_rows) {
+        *reinterpret_cast<float4*>(
+            drhs_out + (span.row0 + s0 + t) * kGdnW + v0 + c4) =
+            *reinterpret_cast<const float4*>(&L.dx[t][c4]);
+      }
+    }
+
+    // ---- dS = e^{g_tot} dS + EK^T @ (-beta drhs) + EQ^T @ dO, in registers
+    wide_scale<false>(L.wq, L.qc, L.gc, g_tot, c_rows);
+    {
+      const float e_tot = __builtin_amdgcn_exp2f(g_tot * kLog2eG);
+#pragma unroll
+      for (int a = 0; a < TK; ++a) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) dS[a][b] *= e_tot;
+      }
+      for (int t = 0; t < c_rows; ++t) {
+        const float bt = L.beta[t];
+        const float4 xv = *reinterpret_cast<const float4*>(&L.dx[t][dv0]);
+        const float x4[4] = {bt * xv.x, bt * xv.y, bt * xv.z, bt * xv.w};
+#pragma unroll
+        for (int a = 0; a < TK; ++a) {
+          const float kv = (float)L.ek[t][dk0 + a];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) dS[a][b] -= kv * x4[b];
+        }
+      }
+    }
+    leaf_barrier();
+    for (int t = 0; t < c_rows; ++t) {
+      const bf16x4 dv4 = *reinterpret_cast<const bf16x4*>(&L.doc[t][dv0]);
+#pragma unroll
+      for (int a = 0; a < TK; ++a) {
+        const float qv = (float)L.wq[t][dk0 + a];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) dS[a][b] += qv * (float)dv4[b];
+      }
+    }
+    wide_state_store<TK>(ds0_out + (span.chunk0 + ch) * (int64_t)kGdnW * kGdnW,
+                         dS, dk0, v0 + dv0);
+    leaf_barrier();
+  }
+}
+
 }  // namespace d9d
 
 // ---------------------------------------------------------------------------
@@ -1511,12 +2114,64 @@ void conv_bwd_checks(const torch::Tensor& x, const torch::Tensor& w,
 // duplicated K-side work is cheaper than idle CUs.
 bool gdn_split_dv(int64_t n_wg) { return n_wg * 2 <= 384; }
 
+// D = 128: a workgroup takes a whole CU (120-145 KB of LDS). Four Dv slices
+// of 32 repeat the K-side work four times per head, so they are only taken
+// while 4 n_wg workgroups still run in one pass over the 256 CUs; beyond
+// that two slices of 64 do less work in the same number of passes.
+bool gdn_wide_quarter_dv(int64_t n_wg) { return n_wg * 4 <= 256; }
+
+template <int DVT, bool VARLEN, class... Args>
+void gdn_fwd_wide_launch(int64_t n_wg, Args... args) {
+  auto kern = &d9d::gdn_chunk_fwd_wide_kernel<DVT, VARLEN>;
+  static bool attr_set = false;   // one per instantiation
+  if (!attr_set) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                        (int)sizeof(d9d::GdnWideLds<DVT>));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)n_wg, d9d::kGdnW / DVT),
+                     dim3(d9d::kGdnWT), sizeof(d9d::GdnWideLds<DVT>),
+                     at::hip::getCurrentHIPStream(), args...);
+}
+
+template <int DVT, bool VARLEN, class... Args>
+void gdn_bwd_scan_wide_launch(int64_t n_wg, Args... args) {
+  auto kern = &d9d::gdn_chunk_bwd_scan_wide_kernel<DVT, VARLEN>;
+  static bool attr_set = false;   // one per instantiation
+  if (!attr_set) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                        (int)sizeof(d9d::GdnWideBwdLds<DVT>));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)n_wg, d9d::kGdnW / DVT),
+                     dim3(d9d::kGdnWT), sizeof(d9d::GdnWideBwdLds<DVT>),
+                     at::hip::getCurrentHIPStream(), args...);
+}
+
 template <bool VARLEN>
 void gdn_fwd_launch(int64_t n_wg, int64_t S, const torch::Tensor& q,
                     const torch::Tensor& k, const torch::Tensor& v,
                     const torch::Tensor& beta, const torch::Tensor& g,
                     __bf16* out, float* fs, float* r, float* s0,
                     const int* cu, const int* chunk_off, int H, int64_t nc) {
+  if (q.size(-1) == d9d::kGdnW) {
+    if (n_wg == 0) return;
+    auto qp = reinterpret_cast<const __bf16*>(q.data_ptr());
+    auto kp = reinterpret_cast<const __bf16*>(k.data_ptr());
+    auto vp = reinterpret_cast<const __bf16*>(v.data_ptr());
+    if (gdn_wide_quarter_dv(n_wg)) {
+      gdn_fwd_wide_launch<32, VARLEN>(
+          n_wg, qp, kp, vp, beta.data_ptr<float>(), g.data_ptr<float>(), out,
+          fs, r, s0, n_wg, S, cu, chunk_off, H, nc);
+    } else {
+      gdn_fwd_wide_launch<64, VARLEN>(
+          n_wg, qp, kp, vp, beta.data_ptr<float>(), g.data_ptr<float>(), out,
+          fs, r, s0, n_wg, S, cu, chunk_off, H, nc);
+    }
+    return;
+  }
   static bool attr_set = false;
   if (!attr_set) {
     hipFuncSetAttribute(
@@ -1557,6 +2212,22 @@ void gdn_bwd_scan_launch(int64_t n_wg, int64_t S, const torch::Tensor& q,
                          const torch::Tensor& beta, const torch::Tensor& g,
                          float* drhs, float* ds0, const int* cu,
                          const int* chunk_off, int H, int64_t nc) {
+  if (q.size(-1) == d9d::kGdnW) {
+    if (n_wg == 0) return;
+    auto qp = reinterpret_cast<const __bf16*>(q.data_ptr());
+    auto kp = reinterpret_cast<const __bf16*>(k.data_ptr());
+    auto dp = reinterpret_cast<const __bf16*>(dout.data_ptr());
+    if (gdn_wide_quarter_dv(n_wg)) {
+      gdn_bwd_scan_wide_launch<32, VARLEN>(
+          n_wg, qp, kp, dp, beta.data_ptr<float>(), g.data_ptr<float>(), drhs,
+          ds0, n_wg, S, cu, chunk_off, H, nc);
+    } else {
+      gdn_bwd_scan_wide_launch<64, VARLEN>(
+          n_wg, qp, kp, dp, beta.data_ptr<float>(), g.data_ptr<float>(), drhs,
+          ds0, n_wg, S, cu, chunk_off, H, nc);
+    }
+    return;
+  }
   static bool attr_set = false;
   if (!attr_set) {
     hipFuncSetAttribute(
@@ -1594,21 +2265,29 @@ void gdn_bwd_scan_launch(int64_t n_wg, int64_t S, const torch::Tensor& q,
   }
 }
 
-// dense entry points: (B, H, S, 64) bf16 rows + (B, H, S) gates
+// head dims the chunk kernels are built for: 64, and 128 where `wide` (the
+// forward and the reverse scan; the leaf kernel is D = 64 only)
+bool gdn_head_dim_ok(const torch::Tensor& q, bool wide) {
+  return q.dim() == 4 &&
+         (q.size(-1) == 64 || (wide && q.size(-1) == d9d::kGdnW));
+}
+
+// dense entry points: (B, H, S, D) bf16 rows + (B, H, S) gates
 void gdn_dense_checks(const char* who, const torch::Tensor& q,
                       const torch::Tensor& k, const torch::Tensor& v,
                       const torch::Tensor& beta,
-                      const torch::Tensor& decay_log) {
+                      const torch::Tensor& decay_log, bool wide = false) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16, who,
               ": q must be a bf16 device tensor");
   TORCH_CHECK(k.is_cuda() && k.scalar_type() == torch::kBFloat16, who,
               ": k must be a bf16 device tensor");
   TORCH_CHECK(v.is_cuda() && v.scalar_type() == torch::kBFloat16, who,
               ": v / dout must be a bf16 device tensor");
-  TORCH_CHECK(q.dim() == 4 && q.size(-1) == 64, who,
-              " supports (B, H, S, 64)");
+  TORCH_CHECK(gdn_head_dim_ok(q, wide), who,
+              wide ? " supports (B, H, S, 64) and (B, H, S, 128)"
+                   : " supports (B, H, S, 64)");
   TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(), who,
-              ": q, k, v / dout must share one (B, H, S, 64) shape");
+              ": q, k, v / dout must share one (B, H, S, D) shape");
   TORCH_CHECK(beta.is_cuda() && decay_log.is_cuda(), who,
               ": beta and decay_log must be device tensors");
   TORCH_CHECK(beta.dim() == 3 && beta.size(0) == q.size(0) &&
@@ -1617,17 +2296,19 @@ void gdn_dense_checks(const char* who, const torch::Tensor& q,
               who, ": beta and decay_log must be (B, H, S)");
 }
 
-// (1, H, T, 64) bf16 rows + (1, H, T) gates of one packed row
-void gdn_varlen_checks(const torch::Tensor& q, const torch::Tensor& k,
-                       const torch::Tensor& v, const torch::Tensor& beta,
-                       const torch::Tensor& decay_log) {
+// (1, H, T, D) bf16 rows + (1, H, T) gates of one packed row
+void gdn_varlen_checks(const char* who, const torch::Tensor& q,
+                       const torch::Tensor& k, const torch::Tensor& v,
+                       const torch::Tensor& beta,
+                       const torch::Tensor& decay_log, bool wide = false) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(k.is_cuda() && k.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(v.is_cuda() && v.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(q.dim() == 4 && q.size(-1) == 64,
-              "gdn varlen kernels support (1, H, T, 64)");
-  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(),
-              "q, k, v / dout must share one (1, H, T, 64) shape");
+  TORCH_CHECK(gdn_head_dim_ok(q, wide), who,
+              wide ? " supports (1, H, T, 64) and (1, H, T, 128)"
+                   : " supports (1, H, T, 64)");
+  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(), who,
+              ": q, k, v / dout must share one (1, H, T, D) shape");
   TORCH_CHECK(beta.is_cuda() && decay_log.is_cuda());
   TORCH_CHECK(beta.dim() == 3 && beta.size(0) == q.size(0) &&
                   beta.size(1) == q.size(1) && beta.size(2) == q.size(2) &&
@@ -1674,17 +2355,19 @@ std::vector<torch::Tensor> causal_conv_silu_varlen_bwd(
 std::vector<torch::Tensor> gdn_chunk_bwd_scan(
     torch::Tensor q, torch::Tensor k, torch::Tensor dout,
     torch::Tensor beta, torch::Tensor decay_log) {
-  gdn_dense_checks("gdn_chunk_bwd_scan", q, k, dout, beta, decay_log);
+  gdn_dense_checks("gdn_chunk_bwd_scan", q, k, dout, beta, decay_log,
+                   /*wide=*/true);
   auto qc = q.contiguous();
   auto kc = k.contiguous();
   auto dc = dout.contiguous();
   auto bc = beta.to(torch::kFloat32).contiguous();
   auto gc = decay_log.to(torch::kFloat32).contiguous();
   const int64_t B = qc.size(0), H = qc.size(1), S = qc.size(2);
+  const int64_t D = qc.size(3);
   const int64_t nc = (S + 63) / 64;
   auto f32 = torch::dtype(torch::kFloat32).device(q.device());
-  auto drhs = torch::empty({B, H, S, 64}, f32);
-  auto ds0 = torch::empty({B, H, nc, 64, 64}, f32);
+  auto drhs = torch::empty({B, H, S, D}, f32);
+  auto ds0 = torch::empty({B, H, nc, D, D}, f32);
   gdn_bwd_scan_launch<false>(B * H, S, qc, kc, dc, bc, gc,
                              drhs.data_ptr<float>(), ds0.data_ptr<float>(),
                              nullptr, nullptr, 0, 0);
@@ -1694,8 +2377,9 @@ std::vector<torch::Tensor> gdn_chunk_bwd_scan(
 std::vector<torch::Tensor> gdn_chunk_bwd_scan_varlen(
     torch::Tensor q, torch::Tensor k, torch::Tensor dout,
     torch::Tensor beta, torch::Tensor decay_log, torch::Tensor cu_seqlens) {
-  gdn_varlen_checks(q, k, dout, beta, decay_log);
-  const int64_t H = q.size(1), T = q.size(2);
+  gdn_varlen_checks("gdn_chunk_bwd_scan_varlen", q, k, dout, beta, decay_log,
+                    /*wide=*/true);
+  const int64_t H = q.size(1), T = q.size(2), D = q.size(3);
   auto docs = gdn_check_docs(cu_seqlens, q.size(0), T, q.device(),
                              /*with_chunks=*/true);
   auto qc = q.contiguous();
@@ -1704,8 +2388,8 @@ std::vector<torch::Tensor> gdn_chunk_bwd_scan_varlen(
   auto bc = beta.to(torch::kFloat32).contiguous();
   auto gc = decay_log.to(torch::kFloat32).contiguous();
   auto f32 = torch::dtype(torch::kFloat32).device(q.device());
-  auto drhs = torch::empty({1, H, T, 64}, f32);
-  auto ds0 = torch::empty({1, H, docs.nc, 64, 64}, f32);
+  auto drhs = torch::empty({1, H, T, D}, f32);
+  auto ds0 = torch::empty({1, H, docs.nc, D, D}, f32);
   gdn_bwd_scan_launch<true>(docs.nseq * H, T, qc, kc, dc, bc, gc,
                             drhs.data_ptr<float>(), ds0.data_ptr<float>(),
                             docs.cu_dev.data_ptr<int>(),
@@ -1810,7 +2494,7 @@ std::vector<torch::Tensor> gdn_chunk_bwd_leaf_varlen(
     torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
     torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0,
     torch::Tensor cu_seqlens) {
-  gdn_varlen_checks(q, k, v, beta, decay_log);
+  gdn_varlen_checks("gdn_chunk_bwd_leaf_varlen", q, k, v, beta, decay_log);
   const int64_t T = q.size(2);
   auto docs = gdn_check_docs(cu_seqlens, q.size(0), T, q.device(),
                              /*with_chunks=*/false);
@@ -1844,6 +2528,7 @@ std::vector<torch::Tensor> gdn_chunk_fwd_impl(
   auto bc = beta.to(torch::kFloat32).contiguous();
   auto gc = decay_log.to(torch::kFloat32).contiguous();
   const int64_t B = qc.size(0), H = qc.size(1), S = qc.size(2);
+  const int64_t D = qc.size(3);
   auto out = skip_out ? torch::Tensor() : torch::empty_like(vc);
   __bf16* out_ptr =
       skip_out ? nullptr : reinterpret_cast<__bf16*>(out.data_ptr());
@@ -1851,7 +2536,7 @@ std::vector<torch::Tensor> gdn_chunk_fwd_impl(
   torch::Tensor fs;
   float* fs_ptr = nullptr;
   if (return_state) {
-    fs = torch::empty({state_lead[0], state_lead[1], 64, 64}, f32);
+    fs = torch::empty({state_lead[0], state_lead[1], D, D}, f32);
     fs_ptr = fs.data_ptr<float>();
   }
   // aux outputs for the hand-derived backward: per-row solve results R and
@@ -1860,8 +2545,8 @@ std::vector<torch::Tensor> gdn_chunk_fwd_impl(
   float* r_ptr = nullptr;
   float* s0_ptr = nullptr;
   if (return_aux) {
-    r_aux = torch::empty({B, H, S, 64}, f32);
-    s0_aux = torch::empty({B, H, nc, 64, 64}, f32);
+    r_aux = torch::empty({B, H, S, D}, f32);
+    s0_aux = torch::empty({B, H, nc, D, D}, f32);
     r_ptr = r_aux.data_ptr<float>();
     s0_ptr = s0_aux.data_ptr<float>();
   }
@@ -1884,21 +2569,22 @@ std::vector<torch::Tensor> gdn_chunk_fwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor beta, torch::Tensor decay_log, bool return_state,
     bool return_aux, bool skip_out) {
-  gdn_dense_checks("gdn_chunk_fwd", q, k, v, beta, decay_log);
+  gdn_dense_checks("gdn_chunk_fwd", q, k, v, beta, decay_log, /*wide=*/true);
   return gdn_chunk_fwd_impl<false>(
       q, k, v, beta, decay_log, return_state, return_aux, skip_out,
       {q.size(0), q.size(1)}, (q.size(2) + 63) / 64, nullptr, nullptr);
 }
 
-// Packed documents: q, k, v (1, H, T, 64), one workgroup per (document,
-// head), zero state at each document start. Final state (nseq, H, 64, 64);
-// aux r (1, H, T, 64) by packed row, s0 (1, H, NC, 64, 64) by
+// Packed documents: q, k, v (1, H, T, D), D = 64 or 128, one workgroup per
+// (document, head), zero state at each document start. Final state
+// (nseq, H, D, D); aux r (1, H, T, D) by packed row, s0 (1, H, NC, D, D) by
 // chunk_off[doc] + local chunk.
 std::vector<torch::Tensor> gdn_chunk_fwd_varlen(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor beta, torch::Tensor decay_log, torch::Tensor cu_seqlens,
     bool return_state, bool return_aux, bool skip_out) {
-  gdn_varlen_checks(q, k, v, beta, decay_log);
+  gdn_varlen_checks("gdn_chunk_fwd_varlen", q, k, v, beta, decay_log,
+                    /*wide=*/true);
   auto docs = gdn_check_docs(cu_seqlens, q.size(0), q.size(2), q.device(),
                              /*with_chunks=*/true);
   return gdn_chunk_fwd_impl<true>(

@@ -181,12 +181,14 @@ def chunk_gated_delta_rule(
     chunk_size: int = 64,
     cu_seqlens: torch.Tensor | None = None,  # packed documents (B == 1)
 ) -> torch.Tensor:
-    """GPU (Dk = Dv = 64): fused CDNA4 chunk kernel (csrc/gdn.hip) — the
-    fp32 state stays LDS-resident across the chunk loop and every chunk
-    GEMM lands on MFMA; the hand-derived backward runs on three more
-    kernels there (aux forward, reverse scan, per-chunk leaf gradients)
-    when S is a multiple of 64. Other shapes / CPU: the chunked-parallel
-    WY torch path below.
+    """GPU (Dk = Dv = 64 or 128): fused CDNA4 chunk kernel (csrc/gdn.hip) —
+    the fp32 state stays on chip across the chunk loop (LDS at 64,
+    registers at 128) and every chunk GEMM lands on MFMA; when S is a
+    multiple of 64 the hand-derived backward runs on more kernels there:
+    aux forward and reverse scan at both head dims, the per-chunk leaf
+    gradients at 64 (at 128 that stage is batched torch on the kernels'
+    r, s0, drhs, ds0). Other shapes / CPU: the chunked-parallel WY torch
+    path below.
 
     `cu_seqlens` ((nseq+1,) int32, either device) marks packed documents
     along S: the state is zero at each document start and no gradient
@@ -199,8 +201,8 @@ def chunk_gated_delta_rule(
         _check_cu_seqlens(cu_seqlens, q.shape[0], q.shape[2])
     use_kernel = (
         _use_gdn_kernels(q)
-        and q.shape[-1] == 64
-        and v.shape[-1] == 64
+        and q.shape[-1] == v.shape[-1]
+        and q.shape[-1] in (64, 128)
         and chunk_size == 64
     )
     if torch.is_grad_enabled() and any(
@@ -520,11 +522,14 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
     import os
 
     use_scan_kernels = (
-        _use_gdn_kernels(q) and Dk == 64 and Dv == 64 and C == 64 and pad == 0
-        and os.environ.get("D9D_GDN_BWD_SCAN", "1") != "0"
+        _use_gdn_kernels(q) and Dk == Dv and Dk in (64, 128) and C == 64
+        and pad == 0 and os.environ.get("D9D_GDN_BWD_SCAN", "1") != "0"
     )
+    # the leaf kernel exists at D = 64 only; at 128 the torch stage takes the
+    # scan kernels' r, s0, drhs, ds0
     use_leaf_kernel = (
-        use_scan_kernels and os.environ.get("D9D_GDN_BWD_LEAF", "1") != "0"
+        use_scan_kernels and Dk == 64
+        and os.environ.get("D9D_GDN_BWD_LEAF", "1") != "0"
     )
     # the kernels recompute the decay scan and the 64x64 chunk matrices
     # themselves: gc and the prologue exist only for the torch stages
@@ -663,6 +668,10 @@ class LogSigmoidDecayGate(nn.Module):
 
 
 class GatedDeltaNet(nn.Module):
+    """Gated delta-rule linear attention with short convs and an output gate.
+    On the GPU the recurrence runs on the HIP chunk kernels when
+    head_k_dim == head_v_dim is 64 or 128 (Qwen3-Next uses 128)."""
+
     def __init__(
         self,
         hidden_size: int,
