@@ -9,7 +9,6 @@ and pipelining splitgrad).
 """
 
 import enum
-import threading
 from contextlib import contextmanager
 from typing import Iterator
 
@@ -22,11 +21,16 @@ class GradDirection(enum.Enum):
 _ALL_DIRECTIONS = frozenset({GradDirection.INPUTS, GradDirection.WEIGHTS})
 
 
-class GlobalGradContext(threading.local):
-    """Thread-local set of active gradient directions; defaults to both."""
+class GlobalGradContext:
+    """Process-wide set of active gradient directions; defaults to both.
+
+    Not thread-local: the autograd engine runs the backward of CUDA tensors
+    on its own per-device thread, which must see the directions the thread
+    that called backward() has set. (As a threading.local the switch worked
+    for CPU tensors only; on the GPU both directions were always computed.)
+    """
 
     def __init__(self) -> None:
-        super().__init__()
         self._directions: frozenset[GradDirection] = _ALL_DIRECTIONS
 
     @property

@@ -21,6 +21,11 @@
 //     K and N multiples of 8             -> gmm_db_8phase_kernel<BK8, BN8>
 //     otherwise, or D9D_GMM_DB_8PHASE=0  -> gmm_db_kernel
 //
+// gmm_staged_kernel has a second instantiation for K < 8 or N < 8 that loads
+// element by element (a row is shorter than one 8-wide staging unit).
+// Every entry point checks batch_sizes against the tensors before it
+// launches (check_batch_sizes, build_offsets).
+//
 // BN8 / BK8 are 256 or 192, chosen per call to waste the least padding.
 // Every kernel runs 512 threads = 8 waves as 2 (row halves) x 4 (column
 // quarters) on v_mfma_f32_16x16x32_bf16 with fp32 accumulators. The 8-phase
@@ -148,8 +153,23 @@ D9D_DEVICE void glds16(const char* src, char* dst) {
 // that fill is what makes K % 8 != 0 and ragged N work.
 // Keep the if/else shape: written as `if (ok) return val;` hipcc put a
 // vmcnt(0) behind every vector load and both fallbacks ran at half speed.
+//
+// NARROW (col_end < 8, so ld < 8 for every caller): no 8-wide unit lies
+// inside a row, and the clamped vector load would run past the end of the
+// tensor on its last row. Every unit takes the per-element fill instead.
+template <bool NARROW>
 D9D_DEVICE bf16x8 load8_edge(const bf16_t* __restrict__ base, int ld, int row,
                              int row_end, int col, int col_end) {
+  if constexpr (NARROW) {
+    bf16x8 ev = {};
+    if (row < row_end) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (col + j < col_end) ev[j] = base[(int64_t)row * ld + col + j];
+      }
+    }
+    return ev;
+  }
   const bool ok = row < row_end && col + 7 < col_end;
   const int64_t sr = min(row, row_end - 1);
   const int64_t sc = min(col, max(col_end - 8, 0));
@@ -175,12 +195,13 @@ D9D_DEVICE bf16x8 load8_edge(const bf16_t* __restrict__ base, int ld, int row,
 struct StagedBNK {
   bf16x8 reg[3];
 
+  template <bool NARROW>
   D9D_DEVICE void load(const bf16_t* __restrict__ w_e, int k0, int n0, int K,
                        int N) {
 #pragma unroll
     for (int it = 0; it < 3; ++it) {
       const int idx = (threadIdx.x + it * 512) * 8;
-      reg[it] = load8_edge(w_e, K, n0 + idx / kBK, N, k0 + idx % kBK, K);
+      reg[it] = load8_edge<NARROW>(w_e, K, n0 + idx / kBK, N, k0 + idx % kBK, K);
     }
   }
   D9D_DEVICE void store(char* bt_lds) const {
@@ -207,6 +228,7 @@ struct StagedBKN {
   };
   bvec reg[2][2];
 
+  template <bool NARROW>
   D9D_DEVICE void load(const bf16_t* __restrict__ b_e, int k0, int n0, int K,
                        int N) {
 #pragma unroll
@@ -217,7 +239,7 @@ struct StagedBKN {
       const int n = (grp % (kBN / 8)) * 8;
 #pragma unroll
       for (int h = 0; h < 2; ++h)
-        reg[it][h].v = load8_edge(b_e, N, k0 + kk + h, K, n0 + n, N);
+        reg[it][h].v = load8_edge<NARROW>(b_e, N, k0 + kk + h, K, n0 + n, N);
     }
   }
   D9D_DEVICE void store(char* bt_lds) const {
@@ -244,7 +266,7 @@ struct StagedBKN {
   static D9D_DEVICE int swizzle_key(int n) { return (n >> 3) ^ n; }
 };
 
-template <bool B_ROWMAJOR_KN>
+template <bool B_ROWMAJOR_KN, bool NARROW>
 __global__ __launch_bounds__(512, 1) void gmm_staged_kernel(
     const bf16_t* __restrict__ a,    // (T, K)
     const bf16_t* __restrict__ b,    // (E, K, N) if B_ROWMAJOR_KN else (E, N, K)
@@ -284,10 +306,10 @@ __global__ __launch_bounds__(512, 1) void gmm_staged_kernel(
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int idx = (threadIdx.x + it * 512) * 8;
-      a_reg[it] = load8_edge(a, K, wi.row0 + idx / kBK, wi.row_end,
-                             k0 + idx % kBK, K);
+      a_reg[it] = load8_edge<NARROW>(a, K, wi.row0 + idx / kBK, wi.row_end,
+                                     k0 + idx % kBK, K);
     }
-    b_stage.load(b_e, k0, wi.n0, K, N);
+    b_stage.template load<NARROW>(b_e, k0, wi.n0, K, N);
   };
 
   auto store_lds = [&]() {
@@ -771,6 +793,19 @@ __global__ __launch_bounds__(512, 1) void gmm_db_8phase_kernel(
                  lane);
 }
 
+// Columns (c, c + 1) of one row as the halves of a u32, for gmm_db_kernel's
+// staging; a column at or past `cols` reads as zero. Branchless like
+// load8_edge: the load is clamped to the row's last pair and the halves are
+// selected afterwards, so the last column of an odd `cols` comes from the
+// high half of that pair. cols == 1 (uniform per launch) has no pair.
+D9D_DEVICE uint32_t load_pair_edge(const bf16_t* __restrict__ row, int c,
+                                   int cols) {
+  const ushort* r = reinterpret_cast<const ushort*>(row);
+  if (cols == 1) return c == 0 ? (uint32_t)r[0] : 0u;
+  const uint32_t p = *reinterpret_cast<const uint32_t*>(r + min(c, cols - 2));
+  return c + 1 < cols ? p : (c + 1 == cols ? p >> 16 : 0u);
+}
+
 // db[e] = a[rows_e]^T @ g[rows_e]: out (E, K, N).
 // Grid (ceil(N/256), ceil(K/256), E): 256x256 tiles per workgroup -- 8 waves
 // as 2 (k-halves of 128) x 4 (n-quarters of 64) -- looping the expert's rows
@@ -827,19 +862,15 @@ __global__ __launch_bounds__(512, 1) void gmm_db_kernel(
       const int idx = threadIdx.x + it * 512;
       const int d0 = (idx & 127) * 2;
       const int rb = (idx >> 7) * 4;
-      const bool k_ok = k0 + d0 + 1 < K;
-      const bool n_ok = n0 + d0 + 1 < N;
-      const int64_t sk = min((int64_t)(k0 + d0), (int64_t)max(K - 2, 0));
-      const int64_t sn = min((int64_t)(n0 + d0), (int64_t)max(N - 2, 0));
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int g_row = rt + rb + i;
         const bool row_ok = g_row < r_end;
         const int64_t sr = min((int64_t)g_row, (int64_t)max(r_end - 1, 0));
-        const uint32_t pa = *reinterpret_cast<const uint32_t*>(a + sr * K + sk);
-        const uint32_t pg = *reinterpret_cast<const uint32_t*>(g + sr * N + sn);
-        const uint32_t va = (row_ok && k_ok) ? pa : 0u;
-        const uint32_t vg = (row_ok && n_ok) ? pg : 0u;
+        const uint32_t pa = load_pair_edge(a + sr * K, k0 + d0, K);
+        const uint32_t pg = load_pair_edge(g + sr * N, n0 + d0, N);
+        const uint32_t va = row_ok ? pa : 0u;
+        const uint32_t vg = row_ok ? pg : 0u;
         a_c0[it].s[i] = (ushort)(va & 0xffffu);
         a_c1[it].s[i] = (ushort)(va >> 16);
         g_c0[it].s[i] = (ushort)(vg & 0xffffu);
@@ -922,11 +953,38 @@ static std::map<std::tuple<int64_t, int, int>,
                 std::tuple<torch::Tensor, torch::Tensor, int>> g_e1_offsets;
 static std::mutex g_e1_offsets_mu;
 
+// What every entry point requires of batch_sizes before anything reads it;
+// `op` names the entry point in the message. The sizes themselves (no
+// negative entry, sum == rows) are checked where build_offsets walks them.
+static void check_batch_sizes(const torch::Tensor& batch_sizes,
+                              int64_t num_experts, const char* op) {
+  TORCH_CHECK(batch_sizes.device().is_cpu(), op,
+              ": batch_sizes must be a CPU tensor, got ", batch_sizes.device());
+  TORCH_CHECK(batch_sizes.dim() == 1, op, ": batch_sizes must be 1-D, got ",
+              batch_sizes.dim(), "-D");
+  TORCH_CHECK(at::isIntegralType(batch_sizes.scalar_type(), /*includeBool=*/false),
+              op, ": batch_sizes must have an integer dtype, got ",
+              batch_sizes.scalar_type());
+  TORCH_CHECK(batch_sizes.numel() == num_experts, op, ": batch_sizes has ",
+              batch_sizes.numel(), " entries for ", num_experts, " experts");
+}
+
+// Row offsets and m-tile prefix of a call on the device, and the total
+// m-tile count. Raises unless the sizes are non-negative and sum to `rows`
+// (a smaller sum would leave rows of the output unwritten, a larger one
+// would send the kernels past the end of a and out). A call without rows
+// gets undefined tensors and 0 tiles: nothing to launch.
 static std::tuple<torch::Tensor, torch::Tensor, int> build_offsets(
-    torch::Tensor batch_sizes, torch::Device device, int tile_m) {
+    torch::Tensor batch_sizes, torch::Device device, int tile_m, int64_t rows,
+    const char* op) {
   const int E = batch_sizes.numel();
+  auto bs = batch_sizes.to(torch::kInt64).contiguous();
+  const int64_t* p = bs.data_ptr<int64_t>();
   if (E == 1) {
-    const int64_t rows = batch_sizes.to(torch::kInt64).item<int64_t>();
+    TORCH_CHECK(p[0] >= 0, op, ": batch_sizes[0] = ", p[0], " is negative");
+    TORCH_CHECK(p[0] == rows, op, ": sum(batch_sizes) = ", p[0], " but a has ",
+                rows, " rows");
+    if (rows == 0) return {torch::Tensor(), torch::Tensor(), 0};
     const auto key = std::make_tuple(rows, tile_m, (int)device.index());
     std::lock_guard<std::mutex> lock(g_e1_offsets_mu);
     auto it = g_e1_offsets.find(key);
@@ -941,18 +999,24 @@ static std::tuple<torch::Tensor, torch::Tensor, int> build_offsets(
   }
   auto row_off = torch::empty({E + 1}, torch::dtype(torch::kInt32));
   auto mtile_pref = torch::empty({E + 1}, torch::dtype(torch::kInt32));
-  auto bs = batch_sizes.to(torch::kInt64);
-  const int64_t* p = bs.data_ptr<int64_t>();
   int32_t* ro = row_off.data_ptr<int32_t>();
   int32_t* mp = mtile_pref.data_ptr<int32_t>();
-  int rows = 0, tiles = 0;
+  int64_t sum = 0;
+  int tiles = 0;
   for (int e = 0; e < E; ++e) {
-    ro[e] = rows;
+    TORCH_CHECK(p[e] >= 0, op, ": batch_sizes[", e, "] = ", p[e], " is negative");
+    // each entry is checked against `rows` so the running sum cannot wrap
+    TORCH_CHECK(p[e] <= rows - sum, op, ": sum(batch_sizes) exceeds the ",
+                rows, " rows of a at expert ", e);
+    ro[e] = (int32_t)sum;
     mp[e] = tiles;
-    rows += (int)p[e];
+    sum += p[e];
     tiles += (int)((p[e] + tile_m - 1) / tile_m);
   }
-  ro[E] = rows;
+  TORCH_CHECK(sum == rows, op, ": sum(batch_sizes) = ", sum, " but a has ",
+              rows, " rows");
+  if (rows == 0) return {torch::Tensor(), torch::Tensor(), 0};
+  ro[E] = (int32_t)sum;
   mp[E] = tiles;
   // total tile count returned from the CPU copy: reading it from the device
   // tensor (`mtile_pref[E].item()`) is a D2H sync on EVERY call, which
@@ -1019,21 +1083,40 @@ static void launch_8phase(const ForwardArgs& f) {
 template <bool B_ROWMAJOR_KN>
 static void launch_staged(const ForwardArgs& f) {
   const size_t smem = (d9d::kBM * d9d::kBK + d9d::kBN * d9d::kBK) * sizeof(__bf16);
-  launch_forward(d9d::gmm_staged_kernel<B_ROWMAJOR_KN>, d9d::kBN, smem, f);
+  // K < 8 or N < 8: a row of a or of the weight is shorter than one 8-wide
+  // staging unit, so the kernel loads element by element (load8_edge)
+  if (f.a.size(1) < 8 || f.out.size(1) < 8) {
+    launch_forward(d9d::gmm_staged_kernel<B_ROWMAJOR_KN, true>, d9d::kBN, smem, f);
+  } else {
+    launch_forward(d9d::gmm_staged_kernel<B_ROWMAJOR_KN, false>, d9d::kBN, smem, f);
+  }
+}
+
+// Operand checks shared by gmm and gmm_nt: a (T, K) and a 3-D weight with
+// one slice per entry of batch_sizes, both contiguous bf16 on the GPU.
+static void check_forward_operands(const torch::Tensor& a, const torch::Tensor& b,
+                                   const torch::Tensor& batch_sizes,
+                                   const char* op) {
+  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 && a.is_contiguous(),
+              op, ": a must be a contiguous bf16 tensor on the GPU");
+  TORCH_CHECK(b.is_cuda() && b.scalar_type() == torch::kBFloat16 && b.is_contiguous(),
+              op, ": the weight must be a contiguous bf16 tensor on the GPU");
+  TORCH_CHECK(a.dim() == 2, op, ": a must be 2-D (rows, K), got ", a.dim(), "-D");
+  TORCH_CHECK(b.dim() == 3, op, ": the weight must be 3-D, got ", b.dim(), "-D");
+  TORCH_CHECK(a.size(0) <= INT32_MAX, op, ": ", a.size(0), " rows exceed int32");
+  check_batch_sizes(batch_sizes, b.size(0), op);
 }
 
 torch::Tensor gmm(torch::Tensor a, torch::Tensor b, torch::Tensor batch_sizes) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 && a.is_contiguous());
-  TORCH_CHECK(b.is_cuda() && b.scalar_type() == torch::kBFloat16 && b.is_contiguous());
-  TORCH_CHECK(batch_sizes.device().is_cpu());
+  check_forward_operands(a, b, batch_sizes, "gmm");
   const int T = a.size(0), K = a.size(1);
   const int N = b.size(2);
-  TORCH_CHECK(b.size(1) == K, "gmm K mismatch");
+  TORCH_CHECK(b.size(1) == K, "gmm: K mismatch, a has ", K, " columns and b ",
+              b.size(1), " rows per expert");
 
   auto out = torch::empty({(int64_t)T, (int64_t)N}, a.options());
-  if (T == 0) return out;
   auto [row_off, mtile_pref, total_mtiles] =
-      build_offsets(batch_sizes, a.device(), d9d::kBM);
+      build_offsets(batch_sizes, a.device(), d9d::kBM, T, "gmm");
   if (total_mtiles == 0) return out;
   const ForwardArgs f{a, b, out, row_off, mtile_pref, total_mtiles};
 
@@ -1047,17 +1130,15 @@ torch::Tensor gmm(torch::Tensor a, torch::Tensor b, torch::Tensor batch_sizes) {
 }
 
 torch::Tensor gmm_nt(torch::Tensor a, torch::Tensor w, torch::Tensor batch_sizes) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 && a.is_contiguous());
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous());
-  TORCH_CHECK(batch_sizes.device().is_cpu());
+  check_forward_operands(a, w, batch_sizes, "gmm_nt");
   const int T = a.size(0), K = a.size(1);
   const int N = w.size(1);
-  TORCH_CHECK(w.size(2) == K, "gmm_nt K mismatch");
+  TORCH_CHECK(w.size(2) == K, "gmm_nt: K mismatch, a has ", K,
+              " columns and w ", w.size(2));
 
   auto out = torch::empty({(int64_t)T, (int64_t)N}, a.options());
-  if (T == 0) return out;
   auto [row_off, mtile_pref, total_mtiles] =
-      build_offsets(batch_sizes, a.device(), d9d::kBM);
+      build_offsets(batch_sizes, a.device(), d9d::kBM, T, "gmm_nt");
   if (total_mtiles == 0) return out;
   const ForwardArgs f{a, w, out, row_off, mtile_pref, total_mtiles};
 
@@ -1072,8 +1153,18 @@ torch::Tensor gmm_nt(torch::Tensor a, torch::Tensor w, torch::Tensor batch_sizes
 
 torch::Tensor gmm_db(torch::Tensor a, torch::Tensor g, torch::Tensor batch_sizes,
                      int64_t num_experts) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 && a.is_contiguous());
-  TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kBFloat16 && g.is_contiguous());
+  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 && a.is_contiguous(),
+              "gmm_db: a must be a contiguous bf16 tensor on the GPU");
+  TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kBFloat16 && g.is_contiguous(),
+              "gmm_db: g must be a contiguous bf16 tensor on the GPU");
+  TORCH_CHECK(a.dim() == 2 && g.dim() == 2, "gmm_db: a and g must be 2-D, got ",
+              a.dim(), "-D and ", g.dim(), "-D");
+  TORCH_CHECK(g.size(0) == a.size(0), "gmm_db: a has ", a.size(0),
+              " rows but g has ", g.size(0));
+  TORCH_CHECK(a.size(0) <= INT32_MAX, "gmm_db: ", a.size(0), " rows exceed int32");
+  TORCH_CHECK(num_experts >= 0 && num_experts <= INT32_MAX,
+              "gmm_db: num_experts = ", num_experts, " is out of range");
+  check_batch_sizes(batch_sizes, num_experts, "gmm_db");
   const int K = a.size(1), N = g.size(1);
   const int E = (int)num_experts;
 
@@ -1081,10 +1172,9 @@ torch::Tensor gmm_db(torch::Tensor a, torch::Tensor g, torch::Tensor batch_sizes
   // zero-filling empty experts' tiles; only the legacy fallback needs the
   // prefill (it early-returns on empty experts)
   auto db = torch::empty({(int64_t)E, (int64_t)K, (int64_t)N}, a.options());
-  if (a.size(0) == 0) return db;
-  auto [row_off, mtile_pref, total_mtiles_unused] =
-      build_offsets(batch_sizes, a.device(), d9d::kBM);
-  (void)total_mtiles_unused;
+  auto [row_off, mtile_pref, total_mtiles] =
+      build_offsets(batch_sizes, a.device(), d9d::kBM, a.size(0), "gmm_db");
+  if (total_mtiles == 0) return db.zero_();  // no rows: every expert is empty
   auto order_cpu = torch::argsort(batch_sizes.to(torch::kInt64), /*dim=*/0,
                                   /*descending=*/true).to(torch::kInt32);
   auto expert_order = order_cpu.to(a.device(), /*non_blocking=*/true);

@@ -1607,3 +1607,233 @@ def check_silu_packed(run, rows, inter):
     assert_close(out, rout, TOL_SILU, "out")
     assert_close(dx[:, :inter], rda, TOL_SILU, "dx gate half")
     assert_close(dx[:, inter:], rdb, TOL_SILU, "dx up half")
+
+
+# ---------------------------------------------------------------------------
+# Grouped GEMM (gmm, gmm_nt, gmm_db)
+# ---------------------------------------------------------------------------
+
+# Row layouts: the suite's old one; leading, consecutive and trailing empty
+# experts with an exact 256-row tile, a 1-row expert and a ragged last
+# non-empty expert; E == 1 at one row and at two m-tiles plus one row; and
+# wgrad row-chunk counts 0, 1, 1, 1, 2, 3, 5.
+GMM_ROWS_EDGE = (0, 257, 5, 64)
+GMM_ROWS_EMPTY = (0, 0, 256, 1, 0, 300, 0, 0)
+GMM_ROWS_CHUNKS = (0, 1, 63, 64, 65, 129, 320)
+GMM_ROW_LAYOUTS = [GMM_ROWS_EDGE, GMM_ROWS_EMPTY, (1,), (513,)]
+GMM_POISON_ROWS = (64, 5, 129)
+
+# (K, N) per dispatch branch of d9d_amd/csrc/gmm.hip (its header lists the
+# conditions). NT 8-phase takes any N: N < 16 and N % 8 != 0 clamp nearly
+# every staged weight row and store through the scalar tail. BOTH is the NN
+# 8-phase set (N % 16 == 0), run on both layouts: one k-tile, the K % 64 == 32
+# tail with a ragged 256-tile, two 192-tiles. NN staged with K % 32 == 0 is
+# the transposing stage at N % 16 == 8 and N % 8 != 0. STAGED runs on both
+# layouts: K < 8 and N < 8 (element-wise loads), one exact unit, ragged both.
+GMM_NT_8PHASE = [(64, 1), (64, 7), (96, 100), (160, 24), (128, 257)]
+GMM_BOTH_8PHASE = [(64, 16), (96, 208), (160, 272)]
+GMM_NN_STAGED_K32 = [(64, 8), (96, 72), (128, 100)]
+GMM_STAGED = [(1, 1), (7, 5), (8, 8), (72, 200), (100, 72), (65, 193)]
+# wgrad: <192,192>, <192,256>, <256,192>, <256,256> at one 8-wide unit and
+# with both dims ragged; legacy for K or N not a multiple of 8, odd N included
+GMM_DB_8PHASE = [(192, 192), (192, 256), (256, 192), (8, 8), (264, 200)]
+GMM_DB_LEGACY = [(4, 4), (100, 72), (72, 7)]
+# autograd: NT dgrad reduces over N, so (96, 80) takes the staged kernel and
+# (80, 96) the 8-phase one
+GMM_AUTOGRAD = [(96, 80), (80, 96), (64, 192)]
+
+# |got - ref| <= GMM_ULP * |ref| + R * GMM_ACC * S per output element, with
+# R the reduction length (K forward, N dgrad, the expert's rows for wgrad)
+# and S = sum_r |x_r| |y_r| over that reduction in fp64.
+#   First term: the single final rounding of the fp32 sum to bf16. bf16 keeps
+#   8 significant bits, so round-to-nearest is off by at most half an ulp,
+#   2**-8 |ref|; the bound grants one full ulp, 2**-7.
+#   Second term: the products of two bf16 values are exact in fp32 (16
+#   significant bits), so the only other error is the fp32 accumulation. R
+#   round-to-nearest additions in ANY order are off by at most
+#   (R - 1) * 2**-24 * S to first order (each partial sum is at most S in
+#   magnitude and every addition adds a relative 2**-24); the bound grants
+#   twice that, R * 2**-23 * S, and therefore holds for the MFMA's
+#   summation tree, the k-tile order and rocBLAS alike.
+# Derived, not measured: an fp32 matmul of the planted cases rounded once to
+# bf16 peaks at 0.99 of the half-ulp form of this bound.
+GMM_ULP = 2.0 ** -7
+GMM_ACC = 2.0 ** -23
+GMM_BIG = 16.0
+
+
+def _gmm_offsets(sizes):
+    off = [0]
+    for n in sizes:
+        off.append(off[-1] + int(n))
+    return off
+
+
+def gmm_k_columns(K):
+    """The planted reduction indices: the last column, the first column of
+    the last 64-wide k-tile, column 0 (where a read past K lands on the next
+    row), and for K % 64 == 32 the first column of the window [K-64, K-32)
+    that the 8-phase tail tile stages a second time."""
+    cols = {K - 1, 64 * ((K - 1) // 64), 0}
+    if K % 64 == 32 and K > 64:
+        cols.add(K - 64)
+    return sorted(cols)
+
+
+def gmm_case(sizes, K, N, seed=0):
+    """bf16 a (T, K), b (E, K, N), g (T, N) for per-expert row counts `sizes`.
+
+    a is +-16 (sign alternating by row) on gmm_k_columns(K), and b is +-2 on
+    the same reduction rows, signed by n + e: a row multiplied by the
+    neighbouring expert's weights, a dropped last column or a twice-counted
+    window moves the output by 32 or more. b's columns N-1 and
+    16*((N-1)//16) (last column, first column of the last 16-wide subtile)
+    are four times larger. The first and last row of every non-empty expert
+    and its rows 63, 64, 255, 256 carry |a| ~ 8 signed by the expert and
+    g ~ 8: each contributes about 64 to every element of its own db[e], with
+    the opposite sign to its neighbours' rows."""
+    sizes = [int(n) for n in sizes]
+    E, T = len(sizes), sum(sizes)
+    gen = _gen(7000 + seed)
+    a = torch.randn(T, K, generator=gen)
+    b = torch.randn(E, K, N, generator=gen)
+    g = torch.randn(T, N, generator=gen)
+    off = _gmm_offsets(sizes)
+    for e, n in enumerate(sizes):
+        s_e = 1.0 if e % 2 == 0 else -1.0
+        for r in sorted({0, n - 1, 63, 64, 255, 256}):
+            if 0 <= r < n:
+                a[off[e] + r] = s_e * (8.0 + a[off[e] + r])
+                g[off[e] + r] = 8.0 + g[off[e] + r]
+    for c in sorted({N - 1, 16 * ((N - 1) // 16)}):
+        b[:, :, c] *= 4.0
+    row_sign = torch.where(torch.arange(T) % 2 == 0, 1.0, -1.0)
+    ne_sign = torch.where(
+        (torch.arange(N)[None, :] + torch.arange(E)[:, None]) % 2 == 0, 1.0, -1.0)
+    for c in gmm_k_columns(K):
+        a[:, c] = GMM_BIG * row_sign
+        b[:, c, :] = 2.0 * ne_sign
+    return a.to(BF16), b.to(BF16), g.to(BF16)
+
+
+def gmm_ref(a, b, g, sizes):
+    """fp64 per-expert loop over the bf16 inputs. Returns
+    {name: (ref, S)} for out (T, N), da (T, K) and db (E, K, N), with S the
+    sum of |x||y| over the reduction of each element."""
+    a64, b64, g64 = (t.detach().cpu().double() for t in (a, b, g))
+    T, K = a64.shape
+    E, _, N = b64.shape
+    out, s_out = torch.zeros(T, N, dtype=torch.float64), torch.zeros(T, N, dtype=torch.float64)
+    da, s_da = torch.zeros(T, K, dtype=torch.float64), torch.zeros(T, K, dtype=torch.float64)
+    db, s_db = torch.zeros(E, K, N, dtype=torch.float64), torch.zeros(E, K, N, dtype=torch.float64)
+    off = _gmm_offsets(sizes)
+    for e in range(E):
+        r = slice(off[e], off[e + 1])
+        out[r], s_out[r] = a64[r] @ b64[e], a64[r].abs() @ b64[e].abs()
+        da[r], s_da[r] = g64[r] @ b64[e].t(), g64[r].abs() @ b64[e].abs().t()
+        db[e], s_db[e] = a64[r].t() @ g64[r], a64[r].abs().t() @ g64[r].abs()
+    return dict(out=(out, s_out), da=(da, s_da), db=(db, s_db))
+
+
+_GMM_CACHE = {}
+
+
+def gmm_case_and_ref(sizes, K, N, seed=0):
+    """gmm_case and its gmm_ref, computed once per case; callers must not
+    write to the tensors."""
+    key = (tuple(sizes), K, N, seed)
+    if key not in _GMM_CACHE:
+        a, b, g = gmm_case(sizes, K, N, seed)
+        _GMM_CACHE[key] = (a, b, g, gmm_ref(a, b, g, sizes))
+    return _GMM_CACHE[key]
+
+
+def assert_gmm_close(got, ref, S, R, sizes, what, skip_expert=None):
+    """The GMM bound on every element. `got` is row-wise (T, cols) with R an
+    int, or per-expert (E, K, N) with R the expert's row count. A rejected
+    element is reported as expert, row within the expert, column."""
+    assert got.dtype == BF16, (what, got.dtype)
+    got = got.detach().cpu().double()
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    off = _gmm_offsets(sizes)
+    if got.dim() == 3:
+        red = torch.tensor([float(n) for n in sizes], dtype=torch.float64)[:, None, None]
+    else:
+        red = float(R)
+    bound = GMM_ULP * ref.abs() + red * GMM_ACC * S
+    err = (got - ref).abs()
+    ok = err <= bound        # False for NaN
+    if skip_expert is not None:
+        if got.dim() == 3:
+            ok[skip_expert] = True
+        else:
+            ok[off[skip_expert]:off[skip_expert + 1]] = True
+    if bool(ok.all()):
+        return
+    idx = tuple((~ok).nonzero()[0].tolist())
+    if got.dim() == 3:
+        where = f"expert {idx[0]} ({sizes[idx[0]]} rows), k {idx[1]}, n {idx[2]}"
+    else:
+        e = max(i for i in range(len(sizes)) if off[i] <= idx[0] and sizes[i] > 0)
+        where = f"expert {e}, row {idx[0] - off[e]} of {sizes[e]}, column {idx[1]}"
+    raise AssertionError(
+        f"{what}: {int((~ok).sum())}/{ok.numel()} elements outside the bound; first at "
+        f"{where}: got {got[idx].item():.6g}, want {ref[idx].item():.6g}, "
+        f"|err| {err[idx].item():.4g} > bound {bound[idx].item():.4g}"
+    )
+
+
+def gmm_weight(b, layout):
+    """b (E, K, N) as the op of `layout` stores it: "nn" (gmm) as is, "nt"
+    (gmm_nt) as (E, N, K)."""
+    assert layout in ("nn", "nt"), layout
+    return b if layout == "nn" else b.transpose(1, 2).contiguous()
+
+
+def _gmm_what(name, layout, sizes, K, N):
+    return f"gmm {name} {layout} rows={list(sizes)} K={K} N={N}"
+
+
+def check_gmm_fwd(run, layout, sizes, K, N):
+    """run(a, w, batch_sizes) -> out (T, N); w is (E, K, N) for layout "nn"
+    and (E, N, K) for "nt"; batch_sizes is int64 on the CPU."""
+    a, b, _, ref = gmm_case_and_ref(sizes, K, N)
+    out = run(a, gmm_weight(b, layout), torch.tensor(list(sizes), dtype=torch.int64))
+    assert_gmm_close(out, *ref["out"], K, sizes, _gmm_what("out", layout, sizes, K, N))
+
+
+def check_gmm_db(run, sizes, K, N, poison_expert=None):
+    """run(a, g, batch_sizes, E) -> db (E, K, N). Empty experts must come back
+    as exact zeros. With poison_expert, that expert's rows of a are +inf and
+    its rows of g NaN: its own db is not looked at, every other expert's must
+    still meet the bound (one leaked row would make it NaN)."""
+    a, _, g, ref = gmm_case_and_ref(sizes, K, N)
+    if poison_expert is not None:
+        off = _gmm_offsets(sizes)
+        a, g = a.clone(), g.clone()
+        a[off[poison_expert]:off[poison_expert + 1]] = float("inf")
+        g[off[poison_expert]:off[poison_expert + 1]] = float("nan")
+    db = run(a, g, torch.tensor(list(sizes), dtype=torch.int64), len(sizes))
+    what = _gmm_what("db", "wgrad", sizes, K, N)
+    for e, n in enumerate(sizes):
+        if n == 0:
+            assert bool((db[e].detach().cpu().float() == 0).all()), f"{what}: empty expert {e} is not zero"
+    assert_gmm_close(db, *ref["db"], None, sizes, what, skip_expert=poison_expert)
+
+
+def check_gmm_autograd(run, layout, sizes, K, N, inputs=True, weights=True):
+    """run(a, w, g, batch_sizes) -> (out, da, dw) through the autograd op of
+    `layout`, dw in w's own layout. A direction that is switched off
+    (inputs / weights False) must come back as None."""
+    a, b, g, ref = gmm_case_and_ref(sizes, K, N)
+    out, da, dw = run(a, gmm_weight(b, layout), g, torch.tensor(list(sizes), dtype=torch.int64))
+    assert_gmm_close(out, *ref["out"], K, sizes, _gmm_what("out", layout, sizes, K, N))
+    if inputs:
+        assert_gmm_close(da, *ref["da"], N, sizes, _gmm_what("da", layout, sizes, K, N))
+    else:
+        assert da is None, "the input grad was computed although INPUTS is off"
+    if weights:
+        db = dw if layout == "nn" else dw.transpose(1, 2)
+        assert_gmm_close(db, *ref["db"], None, sizes, _gmm_what("dw", layout, sizes, K, N))
+    else:
+        assert dw is None, "the weight grad was computed although WEIGHTS is off"

@@ -20,6 +20,19 @@ def test_grad_context_with_directions():
     assert GLOBAL_GRAD_CONTEXT.computes(GradDirection.WEIGHTS)
 
 
+def test_grad_context_is_seen_from_other_threads():
+    """The autograd engine runs a CUDA backward on its own device thread,
+    which has to see the directions set by the thread that called it."""
+    import threading
+
+    seen = []
+    with GLOBAL_GRAD_CONTEXT.with_directions(GradDirection.INPUTS):
+        t = threading.Thread(target=lambda: seen.append(GLOBAL_GRAD_CONTEXT.directions))
+        t.start()
+        t.join()
+    assert seen == [frozenset({GradDirection.INPUTS})]
+
+
 def test_offload_tensor_identity_preserved_cpu():
     t = torch.randn(4, 4)
     original_id = id(t)

@@ -647,3 +647,178 @@ def test_silu_mul_edges_cpu(n):
 @pytest.mark.parametrize("shape", kr.SILU_PACKED_SHAPES, ids=str)
 def test_silu_mul_packed_edges_cpu(shape):
     kr.check_silu_packed(silu_packed_run("cpu"), *shape)
+
+
+# ---- grouped GEMM ------------------------------------------------------------
+# The CPU paths of ops.gmm / ops.gmm_nt are per-expert torch loops. They run
+# on the bf16 tensors as they are: torch's CPU bf16 matmul accumulates in fp32
+# and rounds once, which meets the bound of kr.assert_gmm_close on every case
+# below, so the fp32-upcast route is not needed.
+
+
+def gmm_fwd_run(device, layout):
+    def run(a, w, batch_sizes):
+        from d9d_amd import ops
+
+        op = ops.gmm if layout == "nn" else ops.gmm_nt
+        return op(a.to(device), w.to(device), batch_sizes)
+
+    return run
+
+
+def gmm_autograd_run(device, layout, direction=None, strided=False, fill=float("nan")):
+    """Forward and backward through the autograd op; `direction` sets
+    GLOBAL_GRAD_CONTEXT for the backward; `strided` passes a and the incoming
+    grad as non-contiguous column slices of wider tensors whose other columns
+    hold `fill`."""
+
+    def run(a, w, g, batch_sizes):
+        from d9d_amd.core.autograd import GLOBAL_GRAD_CONTEXT
+        from d9d_amd import ops
+
+        op = ops.gmm if layout == "nn" else ops.gmm_nt
+        a, w, g = a.to(device), w.to(device), g.to(device)
+        if strided:
+            a_wide = torch.cat([a, torch.full_like(a, fill)], 1)
+            a = a_wide[:, : a.shape[1]]
+            g_wide = torch.stack([g, torch.full_like(g, fill)], 2).flatten(1)
+            g = g_wide[:, ::2]
+            assert not a.is_contiguous() and not g.is_contiguous()
+        a = a.detach().requires_grad_(True)
+        w = w.detach().requires_grad_(True)
+        out = op(a, w, batch_sizes)
+        if direction is None:
+            out.backward(g)
+        else:
+            with GLOBAL_GRAD_CONTEXT.with_directions(direction):
+                out.backward(g)
+        return out.detach(), a.grad, w.grad
+
+    return run
+
+
+GMM_CPU_SHAPES = kr.GMM_BOTH_8PHASE + kr.GMM_STAGED + [(96, 100), (128, 257)]
+
+
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+@pytest.mark.parametrize("shape", GMM_CPU_SHAPES, ids=str)
+def test_gmm_fwd_edges_cpu(shape, layout):
+    for sizes in kr.GMM_ROW_LAYOUTS:
+        kr.check_gmm_fwd(gmm_fwd_run("cpu", layout), layout, sizes, *shape)
+
+
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+@pytest.mark.parametrize("shape", kr.GMM_AUTOGRAD, ids=str)
+def test_gmm_autograd_edges_cpu(shape, layout):
+    for sizes in (kr.GMM_ROWS_EDGE, kr.GMM_ROWS_EMPTY, kr.GMM_ROWS_CHUNKS, (300,)):
+        kr.check_gmm_autograd(gmm_autograd_run("cpu", layout), layout, sizes, *shape)
+    # a finite fill here: torch's CPU bf16 matmul of a strided view returns NaN
+    # when the columns it skips hold NaN (the GPU suite's fill)
+    kr.check_gmm_autograd(
+        gmm_autograd_run("cpu", layout, strided=True, fill=1.0e4), layout,
+        kr.GMM_ROWS_EDGE, *shape)
+
+
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+def test_gmm_grad_direction_gating_cpu(layout):
+    from d9d_amd.core.autograd import GradDirection
+
+    K, N = kr.GMM_AUTOGRAD[0]
+    kr.check_gmm_autograd(
+        gmm_autograd_run("cpu", layout, GradDirection.INPUTS), layout,
+        kr.GMM_ROWS_EDGE, K, N, weights=False)
+    kr.check_gmm_autograd(
+        gmm_autograd_run("cpu", layout, GradDirection.WEIGHTS), layout,
+        kr.GMM_ROWS_EDGE, K, N, inputs=False)
+
+
+def _gmm_loop64(a, w, sizes):
+    """The fp64 loop rounded once to bf16: a correct implementation that the
+    mutants below break in one place each."""
+    out = torch.zeros(a.shape[0], w.shape[2], dtype=torch.float64)
+    start = 0
+    for e, n in enumerate(sizes.tolist()):
+        out[start:start + n] = a[start:start + n].double() @ w[e].double()
+        start += n
+    return out
+
+
+def test_gmm_check_sees_planted_bugs():
+    """The checkers themselves: the exact loop passes, and a dropped last
+    column, the twice-counted overlap window of the K % 64 == 32 tail, a row
+    multiplied by the next expert's weights and a neighbour's row leaking
+    into db[e] all fail."""
+    bf16 = torch.bfloat16
+    sizes = kr.GMM_ROWS_EDGE
+
+    def exact(a, w, bs):
+        return _gmm_loop64(a, w, bs).to(bf16)
+
+    def drop_last_column(a, w, bs):
+        return _gmm_loop64(a[:, :-1], w[:, :-1], bs).to(bf16)
+
+    def double_count_window(a, w, bs):
+        K = a.shape[1]
+        win = slice(K - 64, K - 32)
+        return (_gmm_loop64(a, w, bs) + _gmm_loop64(a[:, win], w[:, win], bs)).to(bf16)
+
+    def neighbour_weights_on_last_row(a, w, bs):
+        out = _gmm_loop64(a, w, bs)
+        end = 0
+        for e, n in enumerate(bs.tolist()):
+            end += n
+            if n and e + 1 < len(bs):
+                out[end - 1] = a[end - 1].double() @ w[e + 1].double()
+        return out.to(bf16)
+
+    def db_exact(a, g, bs, E, leak=False):
+        db = torch.zeros(E, a.shape[1], g.shape[1], dtype=torch.float64)
+        off = [0] + torch.cumsum(bs, 0).tolist()
+        for e in range(E):
+            rows = slice(off[e], off[e + 1] + (1 if leak and off[e + 1] < a.shape[0] else 0))
+            if off[e + 1] > off[e]:
+                db[e] = a[rows].double().t() @ g[rows].double()
+        return db.to(bf16)
+
+    for K, N in [(96, 80), (768, 64)]:
+        kr.check_gmm_fwd(exact, "nn", sizes, K, N)
+        kr.check_gmm_db(db_exact, sizes, K, N)
+        with pytest.raises(AssertionError, match="column"):
+            kr.check_gmm_fwd(drop_last_column, "nn", sizes, K, N)
+        with pytest.raises(AssertionError, match="expert 1, row 256 of 257"):
+            kr.check_gmm_fwd(neighbour_weights_on_last_row, "nn", sizes, K, N)
+        with pytest.raises(AssertionError, match="expert"):
+            kr.check_gmm_db(lambda a, g, bs, E: db_exact(a, g, bs, E, leak=True), sizes, K, N)
+    with pytest.raises(AssertionError, match="column"):
+        kr.check_gmm_fwd(double_count_window, "nn", sizes, 96, 80)
+    # a non-zero empty expert and a NaN from a poisoned neighbour are seen too
+    with pytest.raises(AssertionError, match="empty expert 0"):
+        kr.check_gmm_db(lambda a, g, bs, E: db_exact(a, g, bs, E) + 1, sizes, 96, 80)
+    with pytest.raises(AssertionError, match="expert 0"):
+        kr.check_gmm_db(
+            lambda a, g, bs, E: db_exact(a, g, bs, E, leak=True), kr.GMM_POISON_ROWS, 96, 80,
+            poison_expert=1)
+
+
+def test_gmm_planted_case_is_what_it_says():
+    a, b, g = kr.gmm_case(kr.GMM_ROWS_EDGE, 96, 80)
+    assert kr.gmm_k_columns(96) == [0, 32, 64, 95]
+    for c in kr.gmm_k_columns(96):
+        assert bool((a[:, c].abs() == kr.GMM_BIG).all()) and bool((b[:, c].abs() == 2).all())
+    assert bool((b[0, 95] == -b[1, 95]).all())           # signed by the expert
+    # expert 1 (odd: negative a) holds rows 0..256, expert 2 starts at 257
+    assert a[0, 5] < -4 and a[256, 5] < -4 and a[257, 5] > 4 and abs(a[1, 5]) < 4
+    assert g[255].mean() > 4 and g[64].mean() > 4 and abs(g[65].mean()) < 1
+
+
+def test_gmm_wrappers_need_cpu_batch_sizes():
+    """The Python wrappers assert that batch_sizes lives on the CPU (the host
+    code walks it); a meta tensor stands in for a device one here."""
+    from d9d_amd import ops
+
+    a, b, _ = kr.gmm_case((3, 2), 8, 8)
+    sizes = torch.tensor([3, 2], device="meta")
+    with pytest.raises(AssertionError):
+        ops.gmm(a, b, sizes)
+    with pytest.raises(AssertionError):
+        ops.gmm_nt(a, b.transpose(1, 2).contiguous(), sizes)

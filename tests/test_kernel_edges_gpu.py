@@ -50,6 +50,28 @@ Branch -> test:
   silu_mul_packed grid loop, last columns, I % 8 ....... test_silu_mul_packed_edges,
                                                          test_silu_mul_packed_needs_multiple_of_8
   gdn / conv / silu / adamw-multi argument checks ...... test_*_reject_bad_arguments
+  gmm_nt 8-phase, N < 16, N % 8 != 0, weight row clamp . test_gmm_nt_8phase_narrow_and_odd_n
+  gmm / gmm_nt 8-phase BN8 256 / 192, one k-tile,
+    K % 64 == 32 tail, ragged n-tile ................... test_gmm_8phase_edges
+  gmm staged (transposing stage) at K % 32 == 0 ........ test_gmm_nn_staged_at_k32
+  gmm / gmm_nt staged, K < 8, N < 8 (element-wise
+    loads), K % 8 != 0, ragged N ....................... test_gmm_staged_edges
+  locate_work: empty runs, exact tile, 1 row, E == 1,
+    cached E == 1 offsets hit and missed ............... every gmm forward test (kr.GMM_ROW_LAYOUTS)
+  gmm_db 8-phase <192|256, 192|256>, 1..9 row chunks,
+    legacy gmm_db_kernel, odd N, empty experts zero .... test_gmm_db_edges
+  gmm_db row masking against a poisoned neighbour ...... test_gmm_db_poisoned_neighbour
+  ops.gmm / ops.gmm_nt dgrad staged and 8-phase, wgrad . test_gmm_autograd_edges
+  gmm_nt E == 1 rocBLAS dgrad and wgrad ................ test_gmm_nt_autograd_single_expert
+  GradDirection gating on the autograd device thread ... test_gmm_grad_direction_gating
+  non-contiguous a and incoming grad ................... test_gmm_autograd_non_contiguous
+  same bits from identical launches (counted vmcnt) .... test_gmm_8phase_same_bits_twice,
+                                                         test_gmm_db_same_bits_twice
+  an expert's rows alone == in the grouped launch ...... test_gmm_expert_isolation_bitwise,
+                                                         test_gmm_db_expert_isolation_bitwise
+  D9D_GMM_8PHASE / _NN_8PHASE / _DB_8PHASE = 0 at the
+    8-phase shapes (one child process) ................. test_gmm_opt_out_paths
+  gmm / gmm_nt / gmm_db batch_sizes and rank checks .... test_gmm_reject_bad_arguments
 """
 
 import pytest
@@ -71,6 +93,7 @@ from tests.test_kernel_edges import (
     check_stochastic_adamw_class,
     conv_run,
     gdn_op_run,
+    gmm_autograd_run,
     silu_packed_run,
     silu_run,
 )
@@ -786,3 +809,263 @@ def test_silu_entry_points_reject_bad_arguments():
         with pytest.raises(RuntimeError, match="silu_mul_packed_bwd"):
             call()
             pytest.fail(f"packed: bad call {i} was accepted")
+
+
+# ---- grouped GEMM ------------------------------------------------------------
+
+
+def _sizes(rows):
+    return torch.tensor(list(rows), dtype=torch.int64)
+
+
+def _gmm_fwd_gpu(layout):
+    """The raw extension entry point of `layout`."""
+
+    def run(a, w, batch_sizes):
+        op = _ext().gmm if layout == "nn" else _ext().gmm_nt
+        return op(a.to(DEV), w.to(DEV), batch_sizes)
+
+    return run
+
+
+def _gmm_db_gpu(a, g, batch_sizes, E):
+    return _ext().gmm_db(a.to(DEV), g.to(DEV), batch_sizes, E)
+
+
+def _gmm_fwd_all_layouts(layout, K, N):
+    for rows in kr.GMM_ROW_LAYOUTS:
+        kr.check_gmm_fwd(_gmm_fwd_gpu(layout), layout, rows, K, N)
+    # E == 1 offsets are cached by row count: miss, then hit
+    kr.check_gmm_fwd(_gmm_fwd_gpu(layout), layout, (512,), K, N)
+    kr.check_gmm_fwd(_gmm_fwd_gpu(layout), layout, (513,), K, N)
+
+
+@pytest.mark.parametrize("shape", kr.GMM_NT_8PHASE, ids=str)
+def test_gmm_nt_8phase_narrow_and_odd_n(shape):
+    """gmm_8phase_kernel<BN8, false> with N < 16 and N % 8 != 0: the weight
+    row clamp min(n0 + nrow, N - 1) with nearly every row clamped, and the
+    scalar store tail."""
+    _gmm_fwd_all_layouts("nt", *shape)
+
+
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+@pytest.mark.parametrize("shape", kr.GMM_BOTH_8PHASE, ids=str)
+def test_gmm_8phase_edges(shape, layout):
+    """Both 8-phase layouts at N % 16 == 0: one k-tile at the narrowest N,
+    the K % 64 == 32 tail, a ragged 256-tile and two 192-tiles."""
+    _gmm_fwd_all_layouts(layout, *shape)
+
+
+@pytest.mark.parametrize("shape", kr.GMM_NN_STAGED_K32, ids=str)
+def test_gmm_nn_staged_at_k32(shape):
+    """gmm_staged_kernel<true> at K % 32 == 0, where only N % 16 != 0 keeps
+    gmm off the 8-phase kernel: the transposing stage at N % 16 == 8 and
+    N % 8 != 0."""
+    _gmm_fwd_all_layouts("nn", *shape)
+
+
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+@pytest.mark.parametrize("shape", kr.GMM_STAGED, ids=str)
+def test_gmm_staged_edges(shape, layout):
+    """Both staged kernels: K < 8 and N < 8 (element-wise loads), one exact
+    8-wide unit, and K, N ragged in both dims."""
+    _gmm_fwd_all_layouts(layout, *shape)
+
+
+GMM_DB_ROWS = [kr.GMM_ROWS_EDGE, kr.GMM_ROWS_EMPTY, (1,), (513,), kr.GMM_ROWS_CHUNKS]
+
+
+@pytest.mark.parametrize("shape", kr.GMM_DB_8PHASE + kr.GMM_DB_LEGACY, ids=str)
+def test_gmm_db_edges(shape):
+    """The four gmm_db_8phase_kernel<BK8, BN8> instantiations and the legacy
+    gmm_db_kernel (K or N not a multiple of 8, odd N) over 0, 1, 2, 3, 5 and 9
+    row chunks; empty experts are exact zeros."""
+    for rows in GMM_DB_ROWS:
+        kr.check_gmm_db(_gmm_db_gpu, rows, *shape)
+
+
+@pytest.mark.parametrize("shape", [(192, 256), (100, 72)], ids=str)
+def test_gmm_db_poisoned_neighbour(shape):
+    """Expert 1's rows are +inf in a and NaN in g: db[0] (exactly one row
+    chunk) and db[2] (two chunks and one row) stay finite and within the
+    bound on the 8-phase and on the legacy kernel."""
+    kr.check_gmm_db(_gmm_db_gpu, kr.GMM_POISON_ROWS, *shape, poison_expert=1)
+
+
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+@pytest.mark.parametrize("shape", kr.GMM_AUTOGRAD, ids=str)
+def test_gmm_autograd_edges(shape, layout):
+    """ops.gmm / ops.gmm_nt forward, dgrad and wgrad. The NT dgrad reduces
+    over N: staged at (96, 80), 8-phase at (80, 96) and (64, 192)."""
+    for rows in (kr.GMM_ROWS_EDGE, kr.GMM_ROWS_EMPTY, kr.GMM_ROWS_CHUNKS):
+        kr.check_gmm_autograd(gmm_autograd_run(DEV, layout), layout, rows, *shape)
+
+
+@pytest.mark.parametrize("shape", kr.GMM_AUTOGRAD, ids=str)
+def test_gmm_nt_autograd_single_expert(shape):
+    """E == 1 on gmm_nt: dgrad and wgrad are torch.matmul (rocBLAS)."""
+    kr.check_gmm_autograd(gmm_autograd_run(DEV, "nt"), "nt", (300,), *shape)
+
+
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+def test_gmm_grad_direction_gating(layout):
+    from d9d_amd.core.autograd import GradDirection
+
+    K, N = kr.GMM_AUTOGRAD[0]
+    for rows in (kr.GMM_ROWS_EDGE, (300,)):
+        kr.check_gmm_autograd(
+            gmm_autograd_run(DEV, layout, GradDirection.INPUTS), layout, rows, K, N,
+            weights=False)
+        kr.check_gmm_autograd(
+            gmm_autograd_run(DEV, layout, GradDirection.WEIGHTS), layout, rows, K, N,
+            inputs=False)
+
+
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+def test_gmm_autograd_non_contiguous(layout):
+    """a and the incoming grad are column slices of wider tensors whose other
+    columns hold NaN."""
+    for K, N in kr.GMM_AUTOGRAD[:2]:
+        kr.check_gmm_autograd(
+            gmm_autograd_run(DEV, layout, strided=True), layout, kr.GMM_ROWS_EDGE, K, N)
+
+
+@pytest.mark.parametrize("N", [272, 256])
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+def test_gmm_8phase_same_bits_twice(layout, N):
+    """No atomics: two identical launches return the same bits. Inputs stay
+    on the device between the calls; a counted vmcnt that is one short shows
+    up here as a difference."""
+    op = _ext().gmm if layout == "nn" else _ext().gmm_nt
+    for rows in (kr.GMM_ROWS_EDGE, kr.GMM_ROWS_EMPTY):
+        a, b, _, _ = kr.gmm_case_and_ref(rows, 160, N)
+        a, w = a.to(DEV), kr.gmm_weight(b, layout).to(DEV)
+        first = op(a, w, _sizes(rows))
+        for i in range(3):
+            kr.assert_bitwise(op(a, w, _sizes(rows)), first, f"gmm {layout} N={N} rows={rows} call {i + 2}")
+        kr.check_gmm_fwd(lambda *_: first, layout, rows, 160, N)
+
+
+def test_gmm_db_same_bits_twice():
+    for rows in (kr.GMM_ROWS_EDGE, kr.GMM_ROWS_CHUNKS):
+        a, _, g, _ = kr.gmm_case_and_ref(rows, 192, 256)
+        a, g = a.to(DEV), g.to(DEV)
+        first = _ext().gmm_db(a, g, _sizes(rows), len(rows))
+        for i in range(3):
+            kr.assert_bitwise(
+                _ext().gmm_db(a, g, _sizes(rows), len(rows)), first, f"gmm_db rows={rows} call {i + 2}")
+
+
+@pytest.mark.parametrize("shape", [(160, 272), (160, 256), (96, 208), (100, 72)], ids=str)
+@pytest.mark.parametrize("layout", ["nn", "nt"])
+def test_gmm_expert_isolation_bitwise(layout, shape):
+    """An expert's rows do not depend on what else shares the launch: the
+    rows of expert e from the grouped call equal, bit for bit, a call with
+    batch_sizes = [rows_e] on that expert's rows and weight alone. Both calls
+    cut the expert into m-tiles from its own first row and reduce over k in
+    the same order."""
+    K, N = shape
+    rows = kr.GMM_ROWS_EDGE
+    op = _ext().gmm if layout == "nn" else _ext().gmm_nt
+    a, b, _, _ = kr.gmm_case_and_ref(rows, K, N)
+    a, w = a.to(DEV), kr.gmm_weight(b, layout).to(DEV)
+    grouped = op(a, w, _sizes(rows))
+    start = 0
+    for e, n in enumerate(rows):
+        if n:
+            alone = op(a[start:start + n].contiguous(), w[e:e + 1].contiguous(), _sizes([n]))
+            kr.assert_bitwise(grouped[start:start + n], alone, f"gmm {layout} {shape} expert {e}")
+        start += n
+
+
+def test_gmm_db_expert_isolation_bitwise():
+    rows = kr.GMM_ROWS_EDGE
+    for K, N in [(192, 256), (100, 72)]:
+        a, _, g, _ = kr.gmm_case_and_ref(rows, K, N)
+        a, g = a.to(DEV), g.to(DEV)
+        grouped = _ext().gmm_db(a, g, _sizes(rows), len(rows))
+        start = 0
+        for e, n in enumerate(rows):
+            if n:
+                alone = _ext().gmm_db(
+                    a[start:start + n].contiguous(), g[start:start + n].contiguous(), _sizes([n]), 1)
+                kr.assert_bitwise(grouped[e], alone[0], f"gmm_db ({K}, {N}) expert {e}")
+            start += n
+
+
+def test_gmm_opt_out_paths():
+    """D9D_GMM_8PHASE=0, D9D_GMM_NN_8PHASE=0 and D9D_GMM_DB_8PHASE=0 send
+    the 8-phase shapes to the staged and legacy kernels. The switches are read
+    once per process, so one child process runs them
+    (tests/gmm_fallback_child.py)."""
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    from tests import gmm_fallback_child as child
+
+    env = dict(os.environ, **{flag: "0" for flag in child.FLAGS})
+    try:
+        res = subprocess.run(
+            [sys.executable, "-m", "tests.gmm_fallback_child"], env=env, timeout=300,
+            cwd=Path(__file__).resolve().parent.parent, capture_output=True, text=True)
+    except subprocess.TimeoutExpired as exc:
+        pytest.fail(f"the fallback child hung: {exc.stdout!r}", pytrace=False)
+    assert res.returncode == 0, (
+        f"fallback child exited with {res.returncode}\n{res.stdout}\n{res.stderr[-4000:]}")
+
+
+def test_gmm_reject_bad_arguments():
+    """A batch_sizes that does not describe the tensors, or operands of the
+    wrong rank, raise before anything is launched. The cases that would only
+    leave rows unwritten come first and the ones that would run past the
+    tensors last."""
+    ext = _ext()
+    rows = (3, 0, 5)
+    a, b, g = (t.to(DEV) for t in kr.gmm_case(rows, 64, 16))
+    w = b.transpose(1, 2).contiguous()
+    ok = _sizes(rows)
+    for op, wt in ((ext.gmm, b), (ext.gmm_nt, w)):
+        bad_calls = [
+            lambda: op(a, wt, _sizes((3, 0, 4))),              # sum too small
+            lambda: op(a, wt, _sizes((3, 5))),                  # fewer entries than experts
+            lambda: op(a, wt, _sizes((3, 0, 5, 0))),            # more entries than experts
+            lambda: op(a, wt, ok.float()),
+            lambda: op(a, wt, ok.bool()),
+            lambda: op(a, wt, ok.view(3, 1)),
+            lambda: op(a, wt, ok.to(DEV)),
+            lambda: op(a, wt[0], ok),                           # 2-D weight
+            lambda: op(a[None], wt, ok),                        # 3-D a
+            lambda: op(a[:, :32].contiguous(), wt, ok),         # K mismatch
+            lambda: op(a, wt, _sizes((4, -1, 5))),              # negative entry, right sum
+            lambda: op(a[:0], wt, _sizes((0, 0, 1))),           # no rows, sizes say one
+            lambda: op(a, wt, _sizes((3, 0, 6))),               # sum too large
+            lambda: op(a, wt, _sizes((2 ** 62, 2 ** 62, 8))),   # the sum wraps int64
+        ]
+        for i, call in enumerate(bad_calls):
+            with pytest.raises(RuntimeError, match="gmm"):
+                call()
+                pytest.fail(f"{op.__name__}: bad call {i} was accepted")
+        # all-zero sizes with an empty a stay legal
+        assert op(a[:0], wt, _sizes((0, 0, 0))).shape == (0, 16)
+        kr.assert_bitwise(op(a, wt, ok.int()), op(a, wt, ok), "int32 batch_sizes")
+    bad_calls = [
+        lambda: ext.gmm_db(a, g, _sizes((3, 0, 4)), 3),
+        lambda: ext.gmm_db(a, g, ok, 4),                        # num_experts != numel
+        lambda: ext.gmm_db(a, g, ok, 2),
+        lambda: ext.gmm_db(a, g, ok.float(), 3),
+        lambda: ext.gmm_db(a, g, ok.view(1, 3), 3),
+        lambda: ext.gmm_db(a, g, ok.to(DEV), 3),
+        lambda: ext.gmm_db(a, g[:7].contiguous(), ok, 3),       # g rows != a rows
+        lambda: ext.gmm_db(a[None], g, ok, 3),
+        lambda: ext.gmm_db(a, g[None], ok, 3),
+        lambda: ext.gmm_db(a, g, _sizes((4, -1, 5)), 3),
+        lambda: ext.gmm_db(a, g, _sizes((3, 0, 6)), 3),
+    ]
+    for i, call in enumerate(bad_calls):
+        with pytest.raises(RuntimeError, match="gmm_db"):
+            call()
+            pytest.fail(f"gmm_db: bad call {i} was accepted")
+    empty = ext.gmm_db(a[:0], g[:0], _sizes((0, 0, 0)), 3)
+    assert empty.shape == (3, 64, 16) and bool((empty == 0).all())
