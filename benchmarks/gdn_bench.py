@@ -20,8 +20,8 @@ v = (torch.randn(B, H, S, D, device="cuda") * 0.5).bfloat16()
 beta = torch.rand(B, H, S, device="cuda")
 g = -torch.rand(B, H, S, device="cuda") * 0.2
 
-# backward leaf stage: gdn_chunk_bwd_leaf (D9D_GDN_BWD_LEAF=1) against the
-# torch stage (=0) in one process. Device events around windows of ITERS
+# backward leaf stage: gdn_chunk_bwd_leaf, or gdn_chunk_bwd_leaf_wide with
+# --head-dim 128 (D9D_GDN_BWD_LEAF=1), against the torch stage (=0) in one process. Device events around windows of ITERS
 # calls, the two paths alternating inside every round, so the spread is taken
 # under the same conditions as the medians. `--bwd-leaf` runs only this.
 def bench_bwd_leaf(rounds=9, iters=10):
@@ -72,18 +72,19 @@ def bench_bwd_leaf(rounds=9, iters=10):
     do16 = do.bfloat16()
     r, s0 = ext.gdn_chunk_fwd(q, k, v, beta, g, False, True, True)
     drhs, ds0 = ext.gdn_chunk_bwd_scan(q, k, do16, beta, g)
-    run = lambda flag: ext.gdn_chunk_bwd_leaf(q, k, v, do16, beta, g, r, drhs, s0, ds0)
+    leaf = ext.gdn_chunk_bwd_leaf_wide if D == 128 else ext.gdn_chunk_bwd_leaf
+    run = lambda flag: leaf(q, k, v, do16, beta, g, r, drhs, s0, ds0)
     run("1")
     ts = [window("1") for _ in range(rounds)]
     res["leaf_kernel_alone_ms"] = round(statistics.median(ts), 4)
     # per chunk: q, k, v, dout bf16 + r, drhs fp32 + s0, ds0 fp32 in; dq, dk, dv fp32 out
-    nbytes = B * H * (S // 64) * (4 * 8192 + 2 * 16384 + 2 * 16384 + 3 * 16384)
-    print(f"gdn_chunk_bwd_leaf alone: median {statistics.median(ts):.3f} ms  min {min(ts):.3f}"
+    nbytes = B * H * (S // 64) * (4 * 64 * D * 2 + 2 * 64 * D * 4 + 2 * D * D * 4 + 3 * 64 * D * 4)
+    print(f"{leaf.__name__} alone: median {statistics.median(ts):.3f} ms  min {min(ts):.3f}"
           f"  max {max(ts):.3f}  ({nbytes / statistics.median(ts) / 1e9:.2f} TB/s of {nbytes / 1e9:.2f} GB)")
     print(json.dumps(res))
 
 # head dim 128: the op on the chunk kernels (forward; aux forward + reverse
-# scan + torch leaf stage in the backward) against the torch path it took
+# scan + leaf kernel in the backward) against the torch path it took
 # before they existed (torch WY forward, D9D_GDN_BWD_SCAN=0 backward). Device
 # events around windows of ITERS calls, the two paths alternating inside
 # every round.
@@ -141,7 +142,7 @@ def bench_wide(rounds=7, iters=4):
     os.environ.pop("D9D_GDN_BWD_SCAN")
     print(json.dumps(res))
 
-if D == 128:
+if D == 128 and "--bwd-leaf" not in sys.argv:
     bench_wide()
     sys.exit(0)
 

@@ -80,6 +80,16 @@ std::vector<torch::Tensor> gdn_chunk_bwd_leaf_varlen(
     torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
     torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0,
     torch::Tensor cu_seqlens);
+// the same two at head dim 128
+std::vector<torch::Tensor> gdn_chunk_bwd_leaf_wide(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
+    torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
+    torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0);
+std::vector<torch::Tensor> gdn_chunk_bwd_leaf_wide_varlen(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
+    torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
+    torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0,
+    torch::Tensor cu_seqlens);
 
 torch::Tensor cce_dlogits_(torch::Tensor logits, torch::Tensor lse, torch::Tensor targets,
                            torch::Tensor dl, c10::optional<torch::Tensor> dlse,
@@ -131,6 +141,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "chunked gated delta rule backward per-chunk leaf gradients (GDN)");
   m.def("gdn_chunk_bwd_leaf_varlen", &gdn_chunk_bwd_leaf_varlen,
         "chunked gated delta rule backward per-chunk leaf gradients, packed documents (GDN)");
+  m.def("gdn_chunk_bwd_leaf_wide", &gdn_chunk_bwd_leaf_wide,
+        "GDN backward per-chunk leaf gradients at head dim 128");
+  m.def("gdn_chunk_bwd_leaf_wide_varlen", &gdn_chunk_bwd_leaf_wide_varlen,
+        "GDN backward per-chunk leaf gradients at head dim 128, packed documents");
   m.def("adamw_stochastic_bf16_multi_", &adamw_stochastic_bf16_multi_, "multi-tensor fused SR-AdamW");
   m.def("gmm", &gmm, "CDNA4 grouped GEMM (MoE experts)");
   m.def("gmm_nt", &gmm_nt, "CDNA4 grouped GEMM, weight (E,N,K)");

@@ -19,9 +19,11 @@
 //    (document, head) from a zero state, conv taps clipped at the
 //    document start; the leaf kernel takes a last-chunk-of-document flag.
 //    cu_seqlens is validated on the host before launch.
-// 5. Dk = Dv = 128 variants of the forward (with its aux outputs) and the
-//    reverse scan, dense and packed: 8-wave workgroups with the fp32 state
-//    in registers (the `wide` section below). The leaf kernel is D = 64 only.
+// 5. Dk = Dv = 128 variants of the forward (with its aux outputs), the
+//    reverse scan and the leaf gradients, dense and packed: 8-wave
+//    workgroups, the scans with the fp32 state in registers, the leaf kernel
+//    with full-size operand images in 158 KB of LDS (the `wide` sections
+//    below).
 #include "common.h"
 #include "mfma.h"
 
@@ -1986,6 +1988,464 @@ __attribute__((target("no-packed-fp32-ops"))) void gdn_chunk_bwd_scan_wide_kerne
   }
 }
 
+// ---------------------------------------------------------------------------
+// chunked gated delta rule backward LEAF GRADIENTS at Dk = Dv = 128
+// ---------------------------------------------------------------------------
+//
+// The algebra, the rowsum(drhs * P) reassociation through G and every
+// rounding point of gdn_chunk_bwd_leaf_kernel (comment above GdnLeafLds), one
+// workgroup per (b, h, chunk) of 64 rows; only the feature dims double: the
+// D-wide products (dwK, dEQ, G, dqk K, dqk^T Q, dkk K, dkk^T K) are 64 x 128,
+// the contractions over D (dwK, dEQ, G, dN, dM, kk, qk) 128 long, and the
+// 64 x 64 matrices keep their size. Laid out for that:
+//
+//   * 8 waves, wave w = (rs = w & 3, nh = w >> 2) as in the kernels above:
+//     rows 16 rs .. 16 rs + 15 of every product, column half nh. A wave keeps
+//     16 x 64 of dq and dk (32 accumulator registers) and a 16 x 32 half of
+//     dN, dM, kk, qk (2 column tiles each), which never leave registers.
+//   * B operands are full-size images at the padded pitches, 158 KB with the
+//     small vectors, one workgroup per CU: K rows, K^T and Q^T, and two hi/lo
+//     pairs reused in phases. `a`: R (64 x 128) -> dqk -> dkk (64 x 64);
+//     `b`: dS1 (128 x 128) -> S0 -> dqk^T -> dkk^T.
+//   * S0 is loaded with dS1 (the <dS1, S0> term wants both) and waits in
+//     32 registers per thread until the dwK product has consumed the dS1
+//     image, then takes its place.
+//   * A fragments: R rows come from the `a` image and K rows from the K tile
+//     (both are staged anyway). dO, drhs and Q rows are read from global
+//     memory by the two waves of a row band: the LDS has no room for a third
+//     image pair, and the second read hits the cache. dV and rowsum(drhs * V)
+//     are split between the two by contraction step, so each dv element is
+//     written once.
+//   * rowsums end in two per-column-half slots, colsum(rr) in one slot per
+//     row band (a (band, column) pair belongs to one wave), the dgc_63 scalar
+//     in eight; wave 0 adds them up and runs the in-chunk reverse cumsum.
+struct GdnWideLeafLds {
+  WideTile kc;                    // K rows        (B of kk, qk; A of kk)
+  bf16_t kT[kGdnW][kGdnCP];       // K^T: kT[d][t] (B of . K; K in C layout)
+  bf16_t qT[kGdnW][kGdnCP];       // Q^T: qT[d][t] (B of . Q; Q in C layout)
+  WideTile a[2];                  // hi/lo: R, then dqk, then dkk
+  bf16_t b[2][kGdnW][kGdnWP];     // hi/lo: dS1, then S0, then dqk^T, dkk^T
+  float gc[kGdnC];
+  float beta[kGdnC];
+  float dgc[2][kGdnC];            // row-owned part of dgc, per column half
+  float db[2][kGdnC];             // C-layout part of dbeta, per column half
+  float dbv[2][kGdnC];            // rowsum(drhs * V), per contraction half
+  float colsum[4][kGdnC];         // colsum(rr), per row band
+  float red[8];                   // per-wave part of the dgc_63 scalar
+};
+static_assert(sizeof(GdnWideLeafLds) <= kGdnLdsMax,
+              "a workgroup has 160 KB of LDS");
+constexpr int kWleafA = kGdnC * kGdnWP;   // elements between the `a` images
+constexpr int kWleafB = kGdnW * kGdnWP;   // elements between the `b` images
+
+// acc[nt] += A . B^T-image over KS contraction steps of 32: A fragments
+// a[ks][image] (NA = 2: hi/lo), B rows brow0 + 16 nt + (lane & 15) of NB
+// images `bimg` elements apart at row pitch PB. Cross terms run smallest
+// first.
+template <int NT, int KS, int NA, int NB, int PB>
+D9D_DEVICE void wleaf_mma(f32x4 (&acc)[NT], const bf16x8 (&a)[KS][NA],
+                          const bf16_t* b, int bimg, int brow0, int lane) {
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int d0 = ks * 32 + (lane >> 4) * 8;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int brow = brow0 + nt * 16 + (lane & 15);
+#pragma unroll
+      for (int ib = NB - 1; ib >= 0; --ib) {
+        const bf16x8 bf =
+            *reinterpret_cast<const bf16x8*>(b + ib * bimg + brow * PB + d0);
+#pragma unroll
+        for (int ia = NA - 1; ia >= 0; --ia) {
+          acc[nt] = mfma16(a[ks][ia], bf, acc[nt]);
+        }
+      }
+    }
+  }
+}
+
+// hi/lo A fragments of row `arow` of an image pair at pitch kGdnWP
+template <int KS>
+D9D_DEVICE void wleaf_afrag(bf16x8 (&a)[KS][2], const bf16_t* img, int aimg,
+                            int arow, int lane) {
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const bf16_t* p = img + arow * kGdnWP + ks * 32 + (lane >> 4) * 8;
+    a[ks][0] = *reinterpret_cast<const bf16x8*>(p);
+    a[ks][1] = *reinterpret_cast<const bf16x8*>(p + aimg);
+  }
+}
+
+// four fp32 values -> hi/lo bf16x4 at p and p + img
+D9D_DEVICE void wleaf_put4(bf16_t* p, int img, const float4& x) {
+  const float xs[4] = {x.x, x.y, x.z, x.w};
+  bf16x4 h4, l4;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    bf16_t h, l;
+    leaf_split(xs[j], h, l);
+    h4[j] = h;
+    l4[j] = l;
+  }
+  *reinterpret_cast<bf16x4*>(p) = h4;
+  *reinterpret_cast<bf16x4*>(p + img) = l4;
+}
+
+// This wave's 16 x 32 block (rows tq .., columns j0 ..) of a C-layout fp32
+// tile -> hi/lo images a[t][j] and b[j][t] (a lane's four rows are one
+// 8-byte store of the transpose).
+D9D_DEVICE void wleaf_put(const f32x4 (&x)[2], GdnWideLeafLds& L, int tq,
+                          int j0, int lane) {
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt) {
+    const int j = j0 + nt * 16 + (lane & 15);
+    bf16x4 h4, l4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      bf16_t h, l;
+      leaf_split(x[nt][r], h, l);
+      L.a[0][tq + r][j] = h;
+      L.a[1][tq + r][j] = l;
+      h4[r] = h;
+      l4[r] = l;
+    }
+    *reinterpret_cast<bf16x4*>(&L.b[0][j][tq]) = h4;
+    *reinterpret_cast<bf16x4*>(&L.b[1][j][tq]) = l4;
+  }
+}
+
+// (built without packed fp32 VALU ops, like the D = 64 leaf kernel)
+__global__ __launch_bounds__(kGdnWT, 1)
+__attribute__((target("no-packed-fp32-ops"))) void gdn_chunk_bwd_leaf_wide_kernel(
+    const bf16_t* __restrict__ q,    // (B, H, Sp, 128), Sp = 64 nc
+    const bf16_t* __restrict__ k,
+    const bf16_t* __restrict__ v,
+    const bf16_t* __restrict__ dout,
+    const float* __restrict__ beta,       // (B, H, Sp)
+    const float* __restrict__ decay_log,  // (B, H, Sp)
+    const float* __restrict__ r_in,       // (B, H, Sp, 128)  gdn_chunk_fwd aux
+    const float* __restrict__ drhs,       // (B, H, Sp, 128)  reverse scan
+    const float* __restrict__ s0,         // (B, H, nc, 128, 128)
+    const float* __restrict__ ds0,        // (B, H, nc, 128, 128)
+    float* __restrict__ dq,               // (B, H, Sp, 128)
+    float* __restrict__ dk,
+    float* __restrict__ dv,
+    float* __restrict__ dbeta,            // (B, H, Sp)
+    float* __restrict__ dg,
+    const int* __restrict__ doc_last,     // (nc,) packed rows only, or nullptr
+    int64_t n_chunks, int64_t nc) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  GdnWideLeafLds& L = *reinterpret_cast<GdnWideLeafLds*>(smem_raw);
+  const bf16_t* La = &L.a[0][0][0];
+  const bf16_t* Lb = &L.b[0][0][0];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int rs = wave & 3;             // row band
+  const int nh = wave >> 2;            // column half
+  const int lr = lane & 15;
+  const int lq = lane >> 4;
+  const int64_t chunk = blockIdx.x;
+  if (chunk >= n_chunks) return;
+  const int64_t c = chunk % nc;
+  // the last chunk of a row / document hands its state to nobody: dS1 = 0
+  // (and ds0[chunk + 1] is never addressed past the end of a row)
+  const bool last = (c == nc - 1) || (doc_last != nullptr && doc_last[c] != 0);
+  const int64_t row0 = chunk * kGdnC;
+  const int64_t tile0 = row0 * kGdnW;
+  const float* s0p = s0 + chunk * (int64_t)(kGdnW * kGdnW);
+  const float* ds1p = ds0 + (chunk + 1) * (int64_t)(kGdnW * kGdnW);
+
+  // ---- stage: decay scan, K / K^T / Q^T, R and dS1 images; S0 to registers
+  if (wave == 0) wide_gates(decay_log + row0, beta + row0, kGdnC, L.gc, L.beta);
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int i = tid + u * kGdnWT;
+    const int row = i >> 4;
+    const int col = (i & 15) * 8;
+    const bf16x8 kv =
+        *reinterpret_cast<const bf16x8*>(k + tile0 + row * kGdnW + col);
+    const bf16x8 qv =
+        *reinterpret_cast<const bf16x8*>(q + tile0 + row * kGdnW + col);
+    *reinterpret_cast<bf16x8*>(&L.kc[row][col]) = kv;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      L.kT[col + j][row] = kv[j];
+      L.qT[col + j][row] = qv[j];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = tid + u * kGdnWT;
+    const int row = i >> 5;
+    const int col = (i & 31) * 4;
+    wleaf_put4(&L.a[0][row][col], kWleafA,
+               *reinterpret_cast<const float4*>(r_in + tile0 + row * kGdnW + col));
+  }
+  float4 s0r[8];
+  float frob = 0.f;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int i = tid + u * kGdnWT;
+    const int row = i >> 5;
+    const int col = (i & 31) * 4;
+    s0r[u] = *reinterpret_cast<const float4*>(s0p + row * kGdnW + col);
+    if (!last) {
+      const float4 d4 =
+          *reinterpret_cast<const float4*>(ds1p + row * kGdnW + col);
+      wleaf_put4(&L.b[0][row][col], kWleafB, d4);
+      frob += d4.x * s0r[u].x + d4.y * s0r[u].y + d4.z * s0r[u].z +
+              d4.w * s0r[u].w;
+    }
+  }
+  leaf_barrier();
+
+  // this lane's rows in the C layout: tq .. tq+3; A fragments: row arow;
+  // D-wide products: columns cb + 16 nt + lr; 64 x 64 ones: jb + 16 nt + lr
+  const int tq = rs * 16 + lq * 4;
+  const int arow = rs * 16 + lr;
+  const int cb = nh * 64;
+  const int jb = nh * 32;
+  const int64_t aoff = tile0 + arow * kGdnW + lq * 8;   // + ks * 32
+  const float g_end = L.gc[kGdnC - 1];
+  const float e_end = expf(g_end);
+  float gct[4], et[4], wt[4], bt[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    gct[r] = L.gc[tq + r];
+    et[r] = expf(gct[r]);
+    wt[r] = expf(g_end - gct[r]);
+    bt[r] = L.beta[tq + r];
+  }
+
+  f32x4 dqa[4], dka[4];
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    dqa[nt] = {0.f, 0.f, 0.f, 0.f};
+    dka[nt] = {0.f, 0.f, 0.f, 0.f};
+  }
+  float rowacc[4] = {0.f, 0.f, 0.f, 0.f};   // dgc partial of rows tq..tq+3
+  float dbacc[4] = {0.f, 0.f, 0.f, 0.f};    // dbeta partial of the same rows
+  float tot = frob * e_end;                 // dgc_63 scalar partial
+
+  // ---- dwK = R dS1^T: dK = w dwK, dw = rowsum(dwK * K) -------------------
+  if (!last) {
+    bf16x8 ar[4][2];
+    wleaf_afrag<4>(ar, La, kWleafA, arow, lane);
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    wleaf_mma<4, 4, 2, 2, kGdnWP>(acc, ar, Lb, kWleafB, cb, lane);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const bf16x4 kf =
+          *reinterpret_cast<const bf16x4*>(&L.kT[cb + nt * 16 + lr][tq]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float dkw = acc[nt][r] * wt[r];
+        dka[nt][r] = dkw;
+        const float p = dkw * (float)kf[r];
+        rowacc[r] -= p;
+        tot += p;
+      }
+    }
+  }
+  leaf_barrier();   // dS1 image consumed: S0 takes its place
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int i = tid + u * kGdnWT;
+    wleaf_put4(&L.b[0][i >> 5][(i & 31) * 4], kWleafB, s0r[u]);
+  }
+
+  // A fragments of dO and drhs (kept for the R^T products); on the way
+  // dV = beta drhs and rowsum(drhs * V) for dbeta, steps 2 nh and 2 nh + 1
+  bf16x8 ado[4][1], adr[4][2];
+  {
+    const float ba = L.beta[arow];
+    float dot = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int64_t off = aoff + ks * 32;
+      ado[ks][0] = *reinterpret_cast<const bf16x8*>(dout + off);
+      float x[8];
+      leaf_load8(drhs + off, x);
+      leaf_split8(x, adr[ks][0], adr[ks][1]);
+      if ((ks >> 1) == nh) {
+        const bf16x8 vv = *reinterpret_cast<const bf16x8*>(v + off);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dot += x[j] * (float)vv[j];
+        *reinterpret_cast<f32x4*>(dv + off) =
+            f32x4{ba * x[0], ba * x[1], ba * x[2], ba * x[3]};
+        *reinterpret_cast<f32x4*>(dv + off + 4) =
+            f32x4{ba * x[4], ba * x[5], ba * x[6], ba * x[7]};
+      }
+    }
+    dot += leaf_shfl(dot, lane ^ 16);
+    dot += leaf_shfl(dot, lane ^ 32);
+    if (lq == 0) L.dbv[nh][arow] = dot;
+  }
+  leaf_barrier();
+
+  // ---- dEQ = dO S0^T: dQ = E dEQ, dgc += E rowsum(dEQ * Q) ---------------
+  {
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    wleaf_mma<4, 4, 1, 2, kGdnWP>(acc, ado, Lb, kWleafB, cb, lane);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const bf16x4 qf =
+          *reinterpret_cast<const bf16x4*>(&L.qT[cb + nt * 16 + lr][tq]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = acc[nt][r] * et[r];
+        dqa[nt][r] = e;
+        rowacc[r] += e * (float)qf[r];
+      }
+    }
+  }
+  // ---- G = drhs S0^T: dK -= beta E G, dgc -= beta E rowsum(G * K),
+  //      dbeta -= E rowsum(G * K) -----------------------------------------
+  {
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    wleaf_mma<4, 4, 2, 2, kGdnWP>(acc, adr, Lb, kWleafB, cb, lane);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const bf16x4 kf =
+          *reinterpret_cast<const bf16x4*>(&L.kT[cb + nt * 16 + lr][tq]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float ge = acc[nt][r] * et[r];
+        const float gk = ge * (float)kf[r];
+        dka[nt][r] -= bt[r] * ge;
+        rowacc[r] -= bt[r] * gk;
+        dbacc[r] -= gk;
+      }
+    }
+  }
+
+  // ---- this wave's half of dN, dM, kk, qk in registers -> dqk (x), dkk (y),
+  //      dbeta, rr sums ------------------------------------------------------
+  f32x4 x[2], y[2];
+  {
+    f32x4 an[2], am[2], akk[2], aqk[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      an[nt] = {0.f, 0.f, 0.f, 0.f};
+      am[nt] = {0.f, 0.f, 0.f, 0.f};
+      akk[nt] = {0.f, 0.f, 0.f, 0.f};
+      aqk[nt] = {0.f, 0.f, 0.f, 0.f};
+    }
+    bf16x8 ak[4][1], aq[4][1];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      ak[ks][0] =
+          *reinterpret_cast<const bf16x8*>(&L.kc[arow][ks * 32 + lq * 8]);
+      aq[ks][0] = *reinterpret_cast<const bf16x8*>(q + aoff + ks * 32);
+    }
+    wleaf_mma<2, 4, 1, 2, kGdnWP>(an, ado, La, kWleafA, jb, lane);
+    wleaf_mma<2, 4, 2, 2, kGdnWP>(am, adr, La, kWleafA, jb, lane);
+    wleaf_mma<2, 4, 1, 1, kGdnWP>(akk, ak, &L.kc[0][0], 0, jb, lane);
+    wleaf_mma<2, 4, 1, 1, kGdnWP>(aqk, aq, &L.kc[0][0], 0, jb, lane);
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int j = jb + nt * 16 + lr;
+      const float gcj = L.gc[j];
+      float colacc = 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = tq + r;
+        // decay ratio only where t >= j, so it stays <= 1
+        const float ratio = (j <= t) ? expf(gct[r] - gcj) : 0.f;
+        const float dn = (j <= t) ? an[nt][r] : 0.f;
+        const float dm = (j < t) ? -am[nt][r] : 0.f;
+        const float dkkr = dm * bt[r];
+        dbacc[r] += dm * akk[nt][r] * ratio;
+        const float rr = (dn * aqk[nt][r] + dkkr * akk[nt][r]) * ratio;
+        rowacc[r] += rr;
+        colacc += rr;
+        x[nt][r] = dn * ratio;
+        y[nt][r] = dkkr * ratio;
+      }
+      colacc += leaf_shfl(colacc, lane ^ 16);
+      colacc += leaf_shfl(colacc, lane ^ 32);
+      if (lq == 0) L.colsum[rs][j] = colacc;
+    }
+  }
+  leaf_barrier();   // R and S0 images consumed
+
+  // ---- dQ += dqk K, dK += dqk^T Q ----------------------------------------
+  wleaf_put(x, L, tq, jb, lane);
+  leaf_barrier();
+  {
+    bf16x8 af[2][2];
+    wleaf_afrag<2>(af, La, kWleafA, arow, lane);
+    wleaf_mma<4, 2, 2, 1, kGdnCP>(dqa, af, &L.kT[0][0], 0, cb, lane);
+    wleaf_afrag<2>(af, Lb, kWleafB, arow, lane);
+    wleaf_mma<4, 2, 2, 1, kGdnCP>(dka, af, &L.qT[0][0], 0, cb, lane);
+  }
+  leaf_barrier();
+
+  // ---- dK += dkk K + dkk^T K ---------------------------------------------
+  wleaf_put(y, L, tq, jb, lane);
+  leaf_barrier();
+  {
+    bf16x8 af[2][2];
+    wleaf_afrag<2>(af, La, kWleafA, arow, lane);
+    wleaf_mma<4, 2, 2, 1, kGdnCP>(dka, af, &L.kT[0][0], 0, cb, lane);
+    wleaf_afrag<2>(af, Lb, kWleafB, arow, lane);
+    wleaf_mma<4, 2, 2, 1, kGdnCP>(dka, af, &L.kT[0][0], 0, cb, lane);
+  }
+
+  // ---- outputs -----------------------------------------------------------
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t off = tile0 + (tq + r) * kGdnW + cb + nt * 16 + lr;
+      dq[off] = dqa[nt][r];
+      dk[off] = dka[nt][r];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+      rowacc[r] += leaf_shfl(rowacc[r], lane ^ off);
+      dbacc[r] += leaf_shfl(dbacc[r], lane ^ off);
+    }
+    if (lr == 0) {
+      L.dgc[nh][tq + r] = rowacc[r];
+      L.db[nh][tq + r] = dbacc[r];
+    }
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) tot += leaf_shfl(tot, lane ^ off);
+  if (lane == 0) L.red[wave] = tot;
+  leaf_barrier();
+  if (wave == 0) {
+    const int t = lane;
+    float dgc = L.dgc[0][t] + L.dgc[1][t] -
+                (L.colsum[0][t] + L.colsum[1][t] + L.colsum[2][t] +
+                 L.colsum[3][t]);
+    if (t == kGdnC - 1) {
+#pragma unroll
+      for (int w = 0; w < 8; ++w) dgc += L.red[w];
+    }
+    // gc = cumsum(g): dg_t = sum of dgc over the rows t .. 63 of the chunk
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float dn = leaf_shfl(dgc, lane + off);
+      if (lane + off < 64) dgc += dn;
+    }
+    dg[row0 + t] = dgc;
+    dbeta[row0 + t] = L.db[0][t] + L.db[1][t] + L.dbv[0][t] + L.dbv[1][t];
+  }
+}
+
 }  // namespace d9d
 
 // ---------------------------------------------------------------------------
@@ -2400,10 +2860,11 @@ std::vector<torch::Tensor> gdn_chunk_bwd_scan_varlen(
 
 namespace {
 
-// Leaf-gradient stage shared by the dense and packed entry points: checks
-// the four scan products against q's (B, H, Sp, 64), allocates the five
-// outputs and launches one workgroup per chunk. `doc_last` is the (nc,)
-// int32 last-chunk-of-a-document flag on the device, or undefined (dense).
+// Leaf-gradient stage shared by the dense and packed entry points at both
+// head dims: checks the four scan products against q's (B, H, Sp, D),
+// allocates the five outputs and launches one workgroup per chunk, the D = 64
+// kernel or the wide one. `doc_last` is the (nc,) int32
+// last-chunk-of-a-document flag on the device, or undefined (dense).
 std::vector<torch::Tensor> gdn_bwd_leaf_impl(
     const char* who, const torch::Tensor& q, const torch::Tensor& k,
     const torch::Tensor& v, const torch::Tensor& dout,
@@ -2411,7 +2872,7 @@ std::vector<torch::Tensor> gdn_bwd_leaf_impl(
     const torch::Tensor& r, const torch::Tensor& drhs,
     const torch::Tensor& s0, const torch::Tensor& ds0,
     const torch::Tensor& doc_last) {
-  const int64_t B = q.size(0), H = q.size(1), S = q.size(2);
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   const int64_t nc = S / 64;
   TORCH_CHECK(dout.is_cuda() && dout.scalar_type() == torch::kBFloat16 &&
                   dout.sizes() == q.sizes(),
@@ -2419,14 +2880,15 @@ std::vector<torch::Tensor> gdn_bwd_leaf_impl(
   for (const torch::Tensor* t : {&r, &drhs}) {
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
                     t->is_contiguous() && t->sizes() == q.sizes(),
-                who, ": r and drhs must be contiguous fp32 (B, H, S, 64)");
+                who, ": r and drhs must be contiguous fp32 (B, H, S, ", D, ")");
   }
   for (const torch::Tensor* t : {&s0, &ds0}) {
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
                     t->is_contiguous() && t->dim() == 5 && t->size(0) == B &&
                     t->size(1) == H && t->size(2) == nc &&
-                    t->size(3) == 64 && t->size(4) == 64,
-                who, ": s0 and ds0 must be contiguous fp32 (B, H, S / 64, 64, 64)");
+                    t->size(3) == D && t->size(4) == D,
+                who, ": s0 and ds0 must be contiguous fp32 (B, H, S / 64, ", D,
+                ", ", D, ")");
   }
   auto qc = q.contiguous();
   auto kc = k.contiguous();
@@ -2435,26 +2897,29 @@ std::vector<torch::Tensor> gdn_bwd_leaf_impl(
   auto bc = beta.to(torch::kFloat32).contiguous();
   auto gc = decay_log.to(torch::kFloat32).contiguous();
   auto f32 = torch::dtype(torch::kFloat32).device(q.device());
-  auto dq = torch::empty({B, H, S, 64}, f32);
-  auto dk = torch::empty({B, H, S, 64}, f32);
-  auto dv = torch::empty({B, H, S, 64}, f32);
+  auto dq = torch::empty({B, H, S, D}, f32);
+  auto dk = torch::empty({B, H, S, D}, f32);
+  auto dv = torch::empty({B, H, S, D}, f32);
   auto dbeta = torch::empty({B, H, S}, f32);
   auto dg = torch::empty({B, H, S}, f32);
   const int64_t n_chunks = B * H * nc;
   if (n_chunks == 0) return {dq, dk, dv, dbeta, dg};
   TORCH_CHECK(n_chunks < (int64_t)1 << 31, who, ": too many chunks for one grid");
 
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&d9d::gdn_chunk_bwd_leaf_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)sizeof(d9d::GdnLeafLds));
-    attr_set = true;
+  const bool wide = D == d9d::kGdnW;
+  auto kern = wide ? &d9d::gdn_chunk_bwd_leaf_wide_kernel
+                   : &d9d::gdn_chunk_bwd_leaf_kernel;
+  const size_t lds =
+      wide ? sizeof(d9d::GdnWideLeafLds) : sizeof(d9d::GdnLeafLds);
+  static bool attr_set[2] = {false, false};   // one per kernel
+  if (!attr_set[wide]) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set[wide] = true;
   }
   auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(d9d::gdn_chunk_bwd_leaf_kernel, dim3((unsigned)n_chunks),
-                     dim3(256), sizeof(d9d::GdnLeafLds), stream,
+  hipLaunchKernelGGL(kern, dim3((unsigned)n_chunks),
+                     dim3(wide ? d9d::kGdnWT : 256), lds, stream,
                      reinterpret_cast<const __bf16*>(qc.data_ptr()),
                      reinterpret_cast<const __bf16*>(kc.data_ptr()),
                      reinterpret_cast<const __bf16*>(vc.data_ptr()),
@@ -2468,6 +2933,35 @@ std::vector<torch::Tensor> gdn_bwd_leaf_impl(
                      doc_last.defined() ? doc_last.data_ptr<int>() : nullptr,
                      n_chunks, nc);
   return {dq, dk, dv, dbeta, dg};
+}
+
+// Packed documents in the chunk-aligned layout the backward gathers into:
+// every cu_seqlens entry is a multiple of 64. Returns the (T / 64,) int32
+// flags of the chunks that end a document, on q's device.
+torch::Tensor gdn_leaf_doc_last(const char* who, const torch::Tensor& q,
+                                const torch::Tensor& cu_seqlens) {
+  const int64_t T = q.size(2);
+  auto docs = gdn_check_docs(cu_seqlens, q.size(0), T, q.device(),
+                             /*with_chunks=*/false);
+  auto cu_cpu = cu_seqlens.cpu().contiguous();
+  const int* cu = cu_cpu.data_ptr<int>();
+  auto last = torch::zeros({T / 64}, torch::dtype(torch::kInt32));
+  int* lp = last.data_ptr<int>();
+  for (int64_t i = 0; i <= docs.nseq; ++i) {
+    TORCH_CHECK(cu[i] % 64 == 0, who, ": cu_seqlens[", i, "] = ", cu[i],
+                " is not a multiple of 64");
+    if (i > 0 && cu[i] > cu[i - 1]) lp[cu[i] / 64 - 1] = 1;
+  }
+  return last.to(q.device());
+}
+
+// head dim exactly 128, for the wide leaf entry points (after the shared
+// checks have established that q is 4-d)
+void gdn_leaf_wide_check(const char* who, const torch::Tensor& q) {
+  TORCH_CHECK(q.size(3) == d9d::kGdnW, who, " supports head dim 128, got ",
+              q.size(3));
+  TORCH_CHECK(q.size(2) % 64 == 0, who, ": S must be a multiple of 64, got ",
+              q.size(2));
 }
 
 }  // namespace
@@ -2486,29 +2980,43 @@ std::vector<torch::Tensor> gdn_chunk_bwd_leaf(
                            decay_log, r, drhs, s0, ds0, torch::Tensor());
 }
 
-// Packed documents in the chunk-aligned layout the backward gathers into:
-// every cu_seqlens entry is a multiple of 64, and the last chunk of each
-// document takes dS1 = 0 instead of the next document's ds0.
+// Packed documents: the last chunk of each document takes dS1 = 0 instead of
+// the next document's ds0.
 std::vector<torch::Tensor> gdn_chunk_bwd_leaf_varlen(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
     torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
     torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0,
     torch::Tensor cu_seqlens) {
-  gdn_varlen_checks("gdn_chunk_bwd_leaf_varlen", q, k, v, beta, decay_log);
-  const int64_t T = q.size(2);
-  auto docs = gdn_check_docs(cu_seqlens, q.size(0), T, q.device(),
-                             /*with_chunks=*/false);
-  auto cu_cpu = cu_seqlens.cpu().contiguous();
-  const int* cu = cu_cpu.data_ptr<int>();
-  auto last = torch::zeros({T / 64}, torch::dtype(torch::kInt32));
-  int* lp = last.data_ptr<int>();
-  for (int64_t i = 0; i <= docs.nseq; ++i) {
-    TORCH_CHECK(cu[i] % 64 == 0, "gdn_chunk_bwd_leaf_varlen: cu_seqlens[", i,
-                "] = ", cu[i], " is not a multiple of 64");
-    if (i > 0 && cu[i] > cu[i - 1]) lp[cu[i] / 64 - 1] = 1;
-  }
-  return gdn_bwd_leaf_impl("gdn_chunk_bwd_leaf_varlen", q, k, v, dout, beta,
-                           decay_log, r, drhs, s0, ds0, last.to(q.device()));
+  const char* who = "gdn_chunk_bwd_leaf_varlen";
+  gdn_varlen_checks(who, q, k, v, beta, decay_log);
+  return gdn_bwd_leaf_impl(who, q, k, v, dout, beta, decay_log, r, drhs, s0,
+                           ds0, gdn_leaf_doc_last(who, q, cu_seqlens));
+}
+
+// The same two at head dim 128 (gdn_chunk_bwd_leaf_wide_kernel): (dq, dk, dv)
+// fp32 (B, H, S, 128), r and drhs (B, H, S, 128), s0 and ds0
+// (B, H, S / 64, 128, 128).
+std::vector<torch::Tensor> gdn_chunk_bwd_leaf_wide(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
+    torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
+    torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0) {
+  const char* who = "gdn_chunk_bwd_leaf_wide";
+  gdn_dense_checks(who, q, k, v, beta, decay_log, /*wide=*/true);
+  gdn_leaf_wide_check(who, q);
+  return gdn_bwd_leaf_impl(who, q, k, v, dout, beta, decay_log, r, drhs, s0,
+                           ds0, torch::Tensor());
+}
+
+std::vector<torch::Tensor> gdn_chunk_bwd_leaf_wide_varlen(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
+    torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
+    torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0,
+    torch::Tensor cu_seqlens) {
+  const char* who = "gdn_chunk_bwd_leaf_wide_varlen";
+  gdn_varlen_checks(who, q, k, v, beta, decay_log, /*wide=*/true);
+  gdn_leaf_wide_check(who, q);
+  return gdn_bwd_leaf_impl(who, q, k, v, dout, beta, decay_log, r, drhs, s0,
+                           ds0, gdn_leaf_doc_last(who, q, cu_seqlens));
 }
 
 namespace {

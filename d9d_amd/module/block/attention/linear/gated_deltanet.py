@@ -185,10 +185,10 @@ def chunk_gated_delta_rule(
     the fp32 state stays on chip across the chunk loop (LDS at 64,
     registers at 128) and every chunk GEMM lands on MFMA; when S is a
     multiple of 64 the hand-derived backward runs on more kernels there:
-    aux forward and reverse scan at both head dims, the per-chunk leaf
-    gradients at 64 (at 128 that stage is batched torch on the kernels'
-    r, s0, drhs, ds0). Other shapes / CPU: the chunked-parallel WY torch
-    path below.
+    aux forward, reverse scan and the per-chunk leaf gradients, each at
+    both head dims (`D9D_GDN_BWD_LEAF=0` puts the leaf stage back on batched
+    torch over the kernels' r, s0, drhs, ds0). Other shapes / CPU: the
+    chunked-parallel WY torch path below.
 
     `cu_seqlens` ((nseq+1,) int32, either device) marks packed documents
     along S: the state is zero at each document start and no gradient
@@ -370,7 +370,8 @@ def _gdn_leaf_grads_torch(Qc, Kc, Vc, dOc, bc, gc, Rs, drhss, S0s, dS1s,
     (B,H,nc,C,Dv), beta and gc = cumsum(g) (B,H,nc,C), chunk entry states S0
     and per-chunk dL/dS1 (B,H,nc,Dk,Dv); `pro` is `_gdn_chunk_prologue` where
     the caller already has it. Returns chunked (dQ, dK, dV, dbeta, dg). The
-    specification of csrc/gdn.hip's gdn_chunk_bwd_leaf kernel."""
+    specification of csrc/gdn.hip's gdn_chunk_bwd_leaf kernels (D = 64 and
+    the wide one at 128)."""
     if pro is None:
         pro = _gdn_chunk_prologue(Qc, Kc, gc)
     E, Eend, w, ratio, kk, qk = pro
@@ -525,11 +526,10 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
         _use_gdn_kernels(q) and Dk == Dv and Dk in (64, 128) and C == 64
         and pad == 0 and os.environ.get("D9D_GDN_BWD_SCAN", "1") != "0"
     )
-    # the leaf kernel exists at D = 64 only; at 128 the torch stage takes the
-    # scan kernels' r, s0, drhs, ds0
+    # one leaf kernel per head dim; with the flag at 0 the torch stage takes
+    # the scan kernels' r, s0, drhs, ds0
     use_leaf_kernel = (
-        use_scan_kernels and Dk == 64
-        and os.environ.get("D9D_GDN_BWD_LEAF", "1") != "0"
+        use_scan_kernels and os.environ.get("D9D_GDN_BWD_LEAF", "1") != "0"
     )
     # the kernels recompute the decay scan and the 64x64 chunk matrices
     # themselves: gc and the prologue exist only for the torch stages
@@ -555,7 +555,9 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
             if use_leaf_kernel:
                 # dS1 = the next chunk's dS0, zero at each document's last
                 # chunk: the kernel reads cu_lay, no shifted copy is made
-                leaf = ext.gdn_chunk_bwd_leaf_varlen(
+                leaf_fn = (ext.gdn_chunk_bwd_leaf_wide_varlen if Dk == 128
+                           else ext.gdn_chunk_bwd_leaf_varlen)
+                leaf = leaf_fn(
                     q16, k16, v16, do16, b32.contiguous(), g32.contiguous(),
                     r_flat, drhs_flat, S0s, dS0s, cu_lay,
                 )
@@ -568,7 +570,9 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
                 q16, k16, do16, b32.contiguous(), g32.contiguous(),
             )
             if use_leaf_kernel:
-                leaf = ext.gdn_chunk_bwd_leaf(
+                leaf_fn = (ext.gdn_chunk_bwd_leaf_wide if Dk == 128
+                           else ext.gdn_chunk_bwd_leaf)
+                leaf = leaf_fn(
                     q16, k16, v16, do16, b32.contiguous(), g32.contiguous(),
                     r_flat, drhs_flat, S0s, dS0s,
                 )
