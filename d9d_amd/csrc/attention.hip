@@ -1225,6 +1225,56 @@ torch::Tensor maybe_pad_d(torch::Tensor t, int D_pad) {
   return padded;
 }
 
+// Argument checks. The entry points are also called from outside the op
+// (parallel/context.py), and the kernels read raw pointers with the strides of
+// a contiguous tensor of the shape the host derives from q, k and v: every
+// check raises with the entry point's name before anything is allocated or
+// launched.
+
+// `t` is a bf16 tensor of `rank` dims on q's CUDA device.
+void check_operand(const torch::Tensor& t, const torch::Tensor& q, int64_t rank,
+                   const char* fn, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16, fn, ": ",
+              name, " must be a bf16 CUDA tensor");
+  TORCH_CHECK(t.device() == q.device(), fn, ": ", name,
+              " is not on q's device");
+  TORCH_CHECK(t.dim() == rank, fn, ": ", name, " must have ", rank,
+              " dims, got ", t.dim());
+}
+
+// q (B, Sq, Hq, D), k (B, Skv, Hkv, D), v (B, Skv, Hkv, Dv), after the varlen
+// unsqueeze.
+void check_qkv_shapes(const torch::Tensor& q, const torch::Tensor& k,
+                      const torch::Tensor& v, const char* fn) {
+  TORCH_CHECK(k.size(0) == q.size(0) && v.size(0) == q.size(0) &&
+                  k.size(3) == q.size(3) && v.size(1) == k.size(1) &&
+                  v.size(2) == k.size(2),
+              fn, ": k/v shape mismatch: q ", q.sizes(), ", k ", k.sizes(),
+              ", v ", v.sizes());
+  TORCH_CHECK(k.size(2) > 0 && q.size(2) % k.size(2) == 0, fn,
+              ": GQA head mismatch, Hq ", q.size(2), " is no multiple of Hkv ",
+              k.size(2));
+}
+
+// One cu_seqlens as int64 on the host: 1-D, integral, starting at 0, never
+// decreasing and ending on the packed row count.
+torch::Tensor checked_cu_seqlens(const torch::Tensor& cu, int64_t total,
+                                 const char* fn, const char* name) {
+  TORCH_CHECK(cu.dim() == 1 && cu.numel() >= 2 &&
+                  at::isIntegralType(cu.scalar_type(), /*includeBool=*/false),
+              fn, ": ", name, " must be a 1-D integer tensor of nseq + 1 entries");
+  auto host = cu.to(torch::kCPU, torch::kLong).contiguous();
+  const int64_t* p = host.data_ptr<int64_t>();
+  const int64_t n = host.numel();
+  TORCH_CHECK(p[0] == 0, fn, ": ", name, " must start at 0, got ", p[0]);
+  for (int64_t i = 1; i < n; ++i) {
+    TORCH_CHECK(p[i] >= p[i - 1], fn, ": ", name, " decreases at entry ", i);
+  }
+  TORCH_CHECK(p[n - 1] == total, fn, ": ", name, " ends at ", p[n - 1],
+              " but the packed tensor has ", total, " rows");
+  return host;
+}
+
 // Varlen launch metadata: device copies of the int32 cu_seqlens and of the
 // per-sequence tile-count prefix that the kernels binary-search. All null / 0
 // for a dense batch.
@@ -1235,13 +1285,25 @@ struct VarlenMeta {
 };
 
 // The grid tiles each sequence's q (tile_kv = false) or kv in `tile` rows.
+// total_q / total_k are the packed row counts the cu_seqlens must end on.
 VarlenMeta prepare_varlen(const c10::optional<torch::Tensor>& cu_seqlens_q,
                           const c10::optional<torch::Tensor>& cu_seqlens_k,
-                          int tile, bool tile_kv, c10::Device device) {
+                          int64_t total_q, int64_t total_k, int tile,
+                          bool tile_kv, c10::Device device, const char* fn) {
   VarlenMeta m;
-  if (!cu_seqlens_q.has_value()) return m;
-  auto cu_q_cpu = cu_seqlens_q->to(torch::kInt32).cpu().contiguous();
-  auto cu_k_cpu = cu_seqlens_k->to(torch::kInt32).cpu().contiguous();
+  if (!cu_seqlens_q.has_value()) {
+    TORCH_CHECK(!cu_seqlens_k.has_value(), fn,
+                ": cu_seqlens_k given without cu_seqlens_q");
+    return m;
+  }
+  TORCH_CHECK(cu_seqlens_k.has_value(), fn,
+              ": cu_seqlens_q given without cu_seqlens_k");
+  auto cu_q_cpu =
+      checked_cu_seqlens(*cu_seqlens_q, total_q, fn, "cu_seqlens_q").to(torch::kInt32);
+  auto cu_k_cpu =
+      checked_cu_seqlens(*cu_seqlens_k, total_k, fn, "cu_seqlens_k").to(torch::kInt32);
+  TORCH_CHECK(cu_q_cpu.numel() == cu_k_cpu.numel(), fn, ": cu_seqlens_q has ",
+              cu_q_cpu.numel(), " entries, cu_seqlens_k ", cu_k_cpu.numel());
   m.nseq = cu_q_cpu.numel() - 1;
   auto pref = torch::empty({m.nseq + 1}, torch::dtype(torch::kInt32));
   const int* cu = (tile_kv ? cu_k_cpu : cu_q_cpu).data_ptr<int>();
@@ -1282,29 +1344,35 @@ std::vector<torch::Tensor> flash_attn_fwd(
     c10::optional<torch::Tensor> cu_seqlens_q,
     c10::optional<torch::Tensor> cu_seqlens_k,
     bool causal, double softmax_scale, int64_t window_left, int64_t q_offset) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
+  constexpr const char* fn = "flash_attn_fwd";
   const bool varlen = cu_seqlens_q.has_value();
+  // varlen packs (total, H, D); dense is (B, S, H, D)
+  const int64_t rank = varlen ? 3 : 4;
+  check_operand(q, q, rank, fn, "q");
+  check_operand(k, q, rank, fn, "k");
+  check_operand(v, q, rank, fn, "v");
   if (varlen) {
-    TORCH_CHECK(q.dim() == 3, "varlen expects (total, H, D)");
     q = q.unsqueeze(0);
     k = k.unsqueeze(0);
     v = v.unsqueeze(0);
   }
-  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4);
+  check_qkv_shapes(q, k, v, fn);
   const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Skv = k.size(1), Hkv = k.size(2), Dv = v.size(3);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA head mismatch");
-  TORCH_CHECK(k.size(3) == D && v.size(1) == Skv && v.size(2) == Hkv,
-              "flash_attn_fwd: k/v shape mismatch");
+  if (sinks.has_value()) {
+    TORCH_CHECK(sinks->is_cuda() && sinks->device() == q.device() &&
+                    sinks->numel() == Hq,
+                fn, ": sinks must hold Hq = ", Hq, " values on q's device");
+  }
 
   const HeadDims pad = padded_head_dims(D, Dv);
+  const int fq = pad.qk > 128 ? d9d::kFwdQWide : d9d::kFwdQ;  // q rows per workgroup
+  const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, Sq, Skv, fq,
+                                       /*tile_kv=*/false, q.device(), fn);
+
   auto qp = maybe_pad_d(q, pad.qk);
   auto kp = maybe_pad_d(k, pad.qk);
   auto vp = maybe_pad_d(v, pad.v);
-
-  const int fq = pad.qk > 128 ? d9d::kFwdQWide : d9d::kFwdQ;  // q rows per workgroup
-  const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, fq,
-                                       /*tile_kv=*/false, q.device());
 
   // the wide pair writes a second plane: O's bf16 rounding residual
   const bool wide = pad.qk > 128;
@@ -1317,7 +1385,6 @@ std::vector<torch::Tensor> flash_attn_fwd(
   torch::Tensor sinks_f;
   if (sinks.has_value()) {
     sinks_f = sinks->to(torch::kFloat32).contiguous();
-    TORCH_CHECK(sinks_f.numel() == Hq, "sinks must be (Hq,)");
     sinks_ptr = sinks_f.data_ptr<float>();
   }
 
@@ -1360,7 +1427,21 @@ std::vector<torch::Tensor> flash_attn_bwd(
     c10::optional<torch::Tensor> cu_seqlens_k,
     bool causal, double softmax_scale, int64_t window_left, int64_t q_offset,
     c10::optional<torch::Tensor> dlse, c10::optional<torch::Tensor> out_lo) {
+  constexpr const char* fn = "flash_attn_bwd";
   const bool varlen = cu_seqlens_q.has_value();
+  const int64_t rank = varlen ? 3 : 4;
+  check_operand(q, q, rank, fn, "q");
+  check_operand(k, q, rank, fn, "k");
+  check_operand(v, q, rank, fn, "v");
+  check_operand(dout, q, rank, fn, "dout");
+  check_operand(out, q, rank, fn, "out");
+  if (out_lo.has_value()) check_operand(*out_lo, q, rank, fn, "out_lo");
+  // lse (B, Hq, Sq), varlen (Hq, total): read through its raw pointer
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() &&
+                  lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
+                  lse.dim() == rank - 1,
+              fn, ": lse must be a contiguous fp32 tensor of ", rank - 1,
+              " dims on q's device");
   if (varlen) {
     if (out_lo.has_value()) out_lo = out_lo->unsqueeze(0);
     dout = dout.unsqueeze(0);
@@ -1370,14 +1451,32 @@ std::vector<torch::Tensor> flash_attn_bwd(
     out = out.unsqueeze(0);
     lse = lse.unsqueeze(0);
   }
+  check_qkv_shapes(q, k, v, fn);
   const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Skv = k.size(1), Hkv = k.size(2), Dv = v.size(3);
-  TORCH_CHECK(k.size(3) == D && out.size(3) == Dv && dout.size(3) == Dv,
-              "flash_attn_bwd: k is as wide as q; out and dout as wide as v");
+  const std::vector<int64_t> o_shape = {B, Sq, Hq, Dv};
+  TORCH_CHECK(out.sizes().equals(o_shape) && dout.sizes().equals(o_shape), fn,
+              ": out and dout must be (B, Sq, Hq, Dv) = ",
+              torch::IntArrayRef(o_shape), ", got out ",
+              out.sizes(), ", dout ", dout.sizes());
+  TORCH_CHECK(!out_lo.has_value() || out_lo->sizes().equals(o_shape), fn,
+              ": out_lo must match out");
+  const std::vector<int64_t> lse_shape = {B, Hq, Sq};
+  TORCH_CHECK(lse.sizes().equals(lse_shape), fn, ": lse must be ",
+              varlen ? "(Hq, total)" : "(B, Hq, Sq)", ", got ", lse.sizes());
+  torch::Tensor dlse_f;
+  if (dlse.has_value()) {
+    TORCH_CHECK(dlse->is_cuda() && dlse->device() == q.device() &&
+                    dlse->dim() == rank - 1,
+                fn, ": dlse must have the layout of lse");
+    dlse_f = varlen ? dlse->unsqueeze(0) : *dlse;
+    TORCH_CHECK(dlse_f.sizes().equals(lse_shape), fn,
+                ": dlse must have the layout of lse");
+  }
   const HeadDims pad = padded_head_dims(D, Dv);
 
-  const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, d9d::kBwdKv,
-                                       /*tile_kv=*/true, q.device());
+  const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, Sq, Skv,
+                                       d9d::kBwdKv, /*tile_kv=*/true, q.device(), fn);
 
   auto qp = maybe_pad_d(q, pad.qk);
   auto kp = maybe_pad_d(k, pad.qk);
@@ -1400,9 +1499,6 @@ std::vector<torch::Tensor> flash_attn_bwd(
   hipMemsetAsync(dv32.data_ptr(), 0, dv32.numel() * sizeof(float), stream);
   if (out_lo.has_value()) {
     // O = out + out_lo (the wide forward's residual): delta as from an fp32 O
-    TORCH_CHECK(out_lo->sizes() == out.sizes() && out_lo->is_cuda() &&
-                    out_lo->scalar_type() == torch::kBFloat16,
-                "flash_attn_bwd: out_lo must match out");
     auto olp = maybe_pad_d(*out_lo, pad.v);
     const int64_t rows = (int64_t)B * Sq * Hq;
     hipLaunchKernelGGL(d9d::attn_delta_lo_kernel, dim3(rows), dim3(64), 0, stream,
@@ -1420,11 +1516,7 @@ std::vector<torch::Tensor> flash_attn_bwd(
   if (dlse.has_value()) {
     // lse is itself an output: d(lse_i)/d(S_ij) = P_ij, so its upstream grad
     // enters as dS = P*(dP - delta) + P*dlse = P*(dP - (delta - dlse)).
-    auto g = dlse->to(torch::kFloat32);
-    if (varlen) g = g.unsqueeze(0);
-    TORCH_CHECK(g.is_cuda() && g.sizes() == delta.sizes(),
-                "flash_attn_bwd: dlse must have the layout of lse");
-    delta.sub_(g);
+    delta.sub_(dlse_f.to(torch::kFloat32));
   }
 
   const dim3 grid(varlen ? vl.n_tiles : (Skv + d9d::kBwdKv - 1) / d9d::kBwdKv,

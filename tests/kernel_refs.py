@@ -1,6 +1,7 @@
 """fp64 references, planted-edge case builders and checkers for the kernel
 edge suite (tests/test_kernel_edges.py on the CPU paths,
-tests/test_kernel_edges_gpu.py on the HIP kernels).
+tests/test_kernel_edges_gpu.py and tests/test_ring_attention_gpu.py on the HIP
+kernels).
 
 References take the bf16/fp32 tensors the kernel sees, upcast to fp64 and run
 the textbook formula; backward references are torch.autograd on that fp64
@@ -847,6 +848,317 @@ def tol_needed(got, ref):
 
 def _scaled(tol, tol_scale):
     return {key: val * tol_scale for key, val in tol.items()}
+
+
+# ---------------------------------------------------------------------------
+# Ring attention: d9d_amd/parallel/context.py on one process
+# ---------------------------------------------------------------------------
+
+# Logit of a planted key. The smallest share of a block's rows that hold
+# under 1e-2 of their mass in a chunk they do not target (check_ring_plant
+# wants 1/8), over the shapes below, in fp64: 0.05 at a logit of 10
+# (attn_case's), 0.137 at 12, 0.227 at 14. The share of rows that live in
+# the targeted chunk is 0.23 at all three.
+RING_LOGIT = 14.0
+# (W, S_local, B, Hq, Hkv, D). Forward tile 128 q x 64 kv rows, backward
+# 128 kv x 64 q rows: 65 is one row past a 64 tile, 128 an exact tile, 130 two
+# rows past it, 64 an exact 64 tile and 1 a single row.
+RING_BLOCK_SHAPES = [
+    (3, 65, 1, 4, 2, 64), (3, 128, 1, 4, 2, 64), (3, 130, 1, 4, 2, 64),
+    (3, 65, 1, 4, 2, 128), (3, 65, 1, 4, 2, 80),
+]
+RING_SHAPES = [
+    (2, 130, 1, 4, 2, 64), (3, 65, 1, 4, 2, 64), (4, 64, 1, 4, 2, 64),
+    (4, 1, 1, 4, 2, 64), (2, 65, 2, 4, 2, 128),
+]
+RING_NONCAUSAL = (3, 65, 1, 4, 2, 64)
+
+
+def ring_case(W, S_local, B, Hq, Hkv, D, seed=0):
+    """bf16 q, k, v, dout (B, W * S_local, H, D) of one causal sequence that W
+    ranks hold in chunks of S_local rows. Keys are planted as in _plant_keys,
+    as a component along q[i] worth a logit of RING_LOGIT, for each query row
+    i = r * S_local + o of chunk r:
+      * the target key in chunk t = i % (r + 1) at the same local offset o
+        (t == r: the causal diagonal), so the targets cycle over every chunk
+        a rank attends to;
+      * where t < r, also the key one past it, t * S_local + o + 1: it lies
+        above the diagonal of its block but is visible, so an off-diagonal
+        block that keeps the causal mask on loses half of the row. On the last
+        row of a chunk it falls into chunk t + 1 and splits the row between
+        two chunks, where a chunk's partial out is far from the final one;
+      * hidden, the key one past the diagonal, i + 1. For the last row of a
+        chunk it is the first key of the next chunk, whose block is skipped
+        (or masked on the last rank's wrap-around)."""
+    g = _gen(6800 + seed)
+    S = W * S_local
+    scale = 1.0 / math.sqrt(D)
+    rep = Hq // Hkv
+    qg = torch.randn(B, S, Hkv, 1, D, generator=g)
+    q = qg.expand(B, S, Hkv, rep, D).reshape(B, S, Hq, D).clone()
+    k = torch.randn(B, S, Hkv, D, generator=g) * 0.3
+    v = torch.randn(B, S, Hkv, D, generator=g)
+    dout = torch.randn(B, S, Hq, D, generator=g)
+    unit = qg[:, :, :, 0] / (qg[:, :, :, 0].pow(2).sum(-1, keepdim=True) * scale) * RING_LOGIT
+    for i in range(S):
+        r, o = divmod(i, S_local)
+        t = i % (r + 1)
+        targets = [t * S_local + o]
+        if t < r:
+            targets.append(t * S_local + o + 1)
+        if i + 1 < S:
+            targets.append(i + 1)
+        for j in targets:
+            k[:, j] += unit[:, i]
+    return dict(
+        q=q.to(BF16), k=k.to(BF16), v=v.to(BF16), dout=dout.to(BF16), sinks=None,
+        causal=True, scale=scale, window_left=-1, q_offset=0, W=W, S_local=S_local,
+    )
+
+
+def ring_noncausal_case(W, S_local, B, Hq, Hkv, D):
+    """attn_case(causal=False) cut into W chunks: every rank attends to every
+    chunk and no block is masked."""
+    case = attn_case(B, W * S_local, W * S_local, Hq, Hkv, D, causal=False)
+    case.update(W=W, S_local=S_local)
+    return case
+
+
+def _ring_chunk(t, r, S_local):
+    return t[:, r * S_local:(r + 1) * S_local]
+
+
+def ring_blocks(case):
+    """The (rank, chunk) blocks the ring computes."""
+    W = case["W"]
+    return [(r, j) for r in range(W) for j in range(W) if j <= r or not case["causal"]]
+
+
+def check_ring_plant(case):
+    """A condition on the inputs (fp64, CPU). For every block (r, j): at least
+    1/8 of the rows of chunk r hold more than half of their softmax mass in
+    chunk j, and for j != r at least 1/8 of them hold less than 1e-2 of it
+    there, which is what separates the merged LSE from chunk j's own by an
+    O(1) error. The hidden decoys are as strong as the planted keys.
+
+    A row has the majority of its mass in one chunk only, so rank r needs
+    r + 1 rows at the least: the two block conditions are asserted where
+    S_local >= W. Below that (the single-row chunks) every row targets its own
+    diagonal and the decoy in the next chunk is what the case checks."""
+    W, S_local = case["W"], case["S_local"]
+    q, k = case["q"].double(), case["k"].double()
+    rep = q.shape[2] // k.shape[2]
+    s = q.permute(0, 2, 1, 3) @ k.permute(0, 2, 1, 3).repeat_interleave(rep, 1).transpose(-1, -2)
+    s = s * case["scale"]
+    S = W * S_local
+    mask = attn_mask(S, S, True, -1, 0)
+    p = torch.softmax(s.masked_fill(mask, float("-inf")), -1)
+    for r, j in ring_blocks(case) if S_local >= W else []:
+        mass = _ring_chunk(p.transpose(1, 2), r, S_local)[..., j * S_local:(j + 1) * S_local].sum(-1)
+        frac_in = float((mass > 0.5).double().mean())
+        assert frac_in >= 0.125, f"block ({r},{j}): {frac_in:.3f} of the rows live in chunk {j}"
+        if j != r:
+            frac_out = float((mass < 1e-2).double().mean())
+            assert frac_out >= 0.125, (
+                f"block ({r},{j}): {frac_out:.3f} of the rows have under 1e-2 in chunk {j}")
+    hidden_top = s.masked_fill(~mask, float("-inf")).max(-1).values
+    visible_top = s.masked_fill(mask, float("-inf")).max(-1).values
+    assert float(hidden_top[hidden_top.isfinite()].median()) > RING_LOGIT - 4.0
+    assert float(visible_top.median()) > RING_LOGIT - 4.0
+
+
+_RING_REF_CACHE = {}
+
+
+def ring_ref(case):
+    """attn_ref of the whole sequence plus the fp64 per-block quantities of
+    every block the ring computes, once per case. ref["blocks"][(r, j)] holds
+      out, lse   chunk j's partial attention of rank r's rows, and
+      dq, dk, dv the block's share of the gradients under _block_bwd's
+                 contract: P = exp(S - lse_full), delta = rowsum(dO * out_full),
+                 dV_j = P^T dO, dS = P * (dO V^T - delta) * scale, dQ_j = dS K,
+                 dK_j = dS^T Q, summed over the GQA group.
+    The shares, summed over the blocks, are asserted to be the autograd
+    gradients of the whole sequence."""
+    key = id(case)
+    if key in _RING_REF_CACHE and _RING_REF_CACHE[key][0] is case:
+        return _RING_REF_CACHE[key][1]
+    ref = attn_ref(case)
+    W, S_local, scale = case["W"], case["S_local"], case["scale"]
+    q, k, v, dout = (case[n].double() for n in ("q", "k", "v", "dout"))
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    rep = Hq // Hkv
+    heads = lambda t: t.permute(0, 2, 1, 3)
+    delta = (dout * ref["out"]).sum(-1).permute(0, 2, 1)          # (B, Hq, S)
+    blocks = {}
+    total = {n: torch.zeros_like(ref[n]) for n in ("dq", "dk", "dv")}
+    for r, j in ring_blocks(case):
+        ch = lambda t, c: _ring_chunk(t, c, S_local)
+        q_r, do_r = heads(ch(q, r)), heads(ch(dout, r))
+        k_j = heads(ch(k, j)).repeat_interleave(rep, 1)
+        v_j = heads(ch(v, j)).repeat_interleave(rep, 1)
+        s = q_r @ k_j.transpose(-1, -2) * scale
+        if case["causal"] and j == r:
+            s = s.masked_fill(attn_mask(S_local, S_local, True, -1, 0), float("-inf"))
+        lse_j = torch.logsumexp(s, -1)
+        out_j = (torch.exp(s - lse_j.unsqueeze(-1)) @ v_j).permute(0, 2, 1, 3)
+        rows = slice(r * S_local, (r + 1) * S_local)
+        p = torch.exp(s - ref["lse"][:, :, rows].unsqueeze(-1))
+        ds = p * (do_r @ v_j.transpose(-1, -2) - delta[:, :, rows].unsqueeze(-1)) * scale
+        group_sum = lambda t: t.view(B, Hkv, rep, S_local, -1).sum(2).permute(0, 2, 1, 3)
+        blk = dict(
+            out=out_j, lse=lse_j, dq=(ds @ k_j).permute(0, 2, 1, 3),
+            dk=group_sum(ds.transpose(-1, -2) @ q_r), dv=group_sum(p.transpose(-1, -2) @ do_r),
+        )
+        blocks[(r, j)] = blk
+        total["dq"][:, rows] += blk["dq"]
+        total["dk"][:, j * S_local:(j + 1) * S_local] += blk["dk"]
+        total["dv"][:, j * S_local:(j + 1) * S_local] += blk["dv"]
+    for n in ("dq", "dk", "dv"):
+        assert_close(total[n], ref[n], dict(rtol=1e-9, atol=1e-9), f"sum of the block {n}")
+    ref["blocks"] = blocks
+    _RING_REF_CACHE[key] = (case, ref)
+    return ref
+
+
+def ring_block_ref(case, r, j):
+    return ring_ref(case)["blocks"][(r, j)]
+
+
+def ring_block_inputs(case, r, j, device):
+    """What rank r hands _block_fwd / _block_bwd for chunk j: its q and dout
+    rows, chunk j's k and v, and the fp64 full-sequence out (as bf16) and lse
+    (as fp32) of its rows, so that a block's error is not mixed with a merge
+    error."""
+    ref = ring_ref(case)
+    S_local = case["S_local"]
+    ch = lambda t, c: _ring_chunk(t, c, S_local).contiguous().to(device)
+    rows = slice(r * S_local, (r + 1) * S_local)
+    return dict(
+        q=ch(case["q"], r), k=ch(case["k"], j), v=ch(case["v"], j),
+        dout=ch(case["dout"], r), out=ch(ref["out"].to(BF16), r),
+        lse=ref["lse"][:, :, rows].float().contiguous().to(device),
+        causal_block=case["causal"] and j == r, scale=case["scale"],
+    )
+
+
+def _report(what, got, ref):
+    print(f"{what}: tol_needed {tol_needed(got, ref):.3g}, max |ref| "
+          f"{float(ref.abs().max()):.3g}")
+
+
+def check_ring_block(block_fwd, block_bwd, case, r, j, device="cpu"):
+    """block_fwd / block_bwd have the signatures of context._block_fwd and
+    context._block_bwd."""
+    x = ring_block_inputs(case, r, j, device)
+    ref = ring_block_ref(case, r, j)
+    out, lse = block_fwd(x["q"], x["k"], x["v"], x["causal_block"], x["scale"])
+    dq, dk, dv = block_bwd(x["q"], x["k"], x["v"], x["out"], x["dout"], x["lse"],
+                           x["causal_block"], x["scale"])
+    got = dict(out=out, lse=lse, dq=dq, dk=dk, dv=dv)
+    for n in got:
+        _report(f"block ({r},{j}) {n}", got[n], ref[n])
+    assert out.dtype == BF16 and lse.dtype == torch.float32
+    assert_close(out, ref["out"], TOL_ATTN_OUT, f"block ({r},{j}) out")
+    assert_close(lse, ref["lse"], TOL_ATTN_LSE, f"block ({r},{j}) lse")
+    assert_close(dq, ref["dq"], TOL_ATTN_DQ, f"block ({r},{j}) dq")
+    assert_close(dk, ref["dk"], TOL_ATTN_GRAD, f"block ({r},{j}) dk")
+    assert_close(dv, ref["dv"], TOL_ATTN_GRAD, f"block ({r},{j}) dv")
+    return got
+
+
+class _RingGroup:
+    """Stands in for the process group of one rank of the virtual ring."""
+
+    def __init__(self, rank, world, queues, failed):
+        self.rank, self.world, self.queues, self.failed = rank, world, queues, failed
+
+
+class _RingCtx:
+    """Stands in for the autograd ctx of _RingAttention."""
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+
+def _virtual_ring_pass(tensors, group):
+    """context._ring_pass between threads: clones go into the next rank's
+    queue, this rank takes what the previous one put into its own. A rank that
+    failed is noticed at once and a silent one after a minute."""
+    import queue
+    import time
+
+    group.queues[(group.rank + 1) % group.world].put([t.clone() for t in tensors])
+    deadline = time.monotonic() + 60.0
+    while True:
+        try:
+            return group.queues[group.rank].get(timeout=0.05)
+        except queue.Empty:
+            if group.failed.is_set() or time.monotonic() > deadline:
+                raise RuntimeError(f"rank {group.rank}: nothing came round the ring") from None
+
+
+def virtual_ring(monkeypatch, case, device, ring_cls=None):
+    """Runs ring_cls.forward and ring_cls.backward (context._RingAttention by
+    default) as W ranks in one process, one thread per rank, on `device`.
+    Only the rank queries and the P2P exchange of context.py are replaced; the
+    skip rule, the online merge, the rotating accumulators and the dtypes
+    handed to the kernels are the shipped code. Returns the per-rank results
+    concatenated along the sequence: out, lse (the merged one the forward
+    saved), dq, dk, dv."""
+    import queue
+    import threading
+
+    from d9d_amd.parallel import context
+
+    ring_cls = ring_cls or context._RingAttention
+    monkeypatch.setattr(context.dist, "get_rank", lambda group=None: group.rank)
+    monkeypatch.setattr(context.dist, "get_world_size", lambda group=None: group.world)
+    monkeypatch.setattr(context, "_ring_pass", _virtual_ring_pass)
+    W, S_local = case["W"], case["S_local"]
+    queues = [queue.Queue() for _ in range(W)]
+    failed = threading.Event()
+    results, errors = [None] * W, []
+
+    def rank_main(rank):
+        try:
+            ch = lambda n: _ring_chunk(case[n], rank, S_local).contiguous().to(device)
+            ctx = _RingCtx()
+            group = _RingGroup(rank, W, queues, failed)
+            out = ring_cls.forward(ctx, ch("q"), ch("k"), ch("v"), group, case["causal"],
+                                   case["scale"])
+            dq, dk, dv = ring_cls.backward(ctx, ch("dout"))[:3]
+            results[rank] = dict(out=out, lse=ctx.saved_tensors[4], dq=dq, dk=dk, dv=dv)
+        except BaseException as exc:  # re-raised in the test below
+            errors.append((rank, exc))
+            failed.set()
+
+    threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(W)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        rank, exc = min(errors, key=lambda e: isinstance(e[1], RuntimeError))
+        raise exc
+    got = {n: torch.cat([res[n] for res in results], 1) for n in ("out", "dq", "dk", "dv")}
+    got["lse"] = torch.cat([res["lse"] for res in results], 2)
+    return got
+
+
+def check_ring(run_ring, case, tol=None):
+    """run_ring(case) -> dict(out, lse, dq, dk, dv) of the whole sequence (see
+    virtual_ring), against attn_ref of the whole sequence."""
+    tol = {**dict(out=TOL_ATTN_OUT, lse=TOL_ATTN_LSE, dq=TOL_ATTN_DQ, dk=TOL_ATTN_GRAD,
+                  dv=TOL_ATTN_GRAD), **(tol or {})}
+    ref = ring_ref(case)
+    got = run_ring(case)
+    for n in ("out", "lse", "dq", "dk", "dv"):
+        _report(f"ring {n}", got[n], ref[n])
+    assert got["out"].dtype == BF16 and got["lse"].dtype == torch.float32
+    for n in ("out", "lse", "dq", "dk", "dv"):
+        assert_close(got[n], ref[n], tol[n], f"ring {n}")
 
 
 # ---------------------------------------------------------------------------

@@ -822,3 +822,184 @@ def test_gmm_wrappers_need_cpu_batch_sizes():
         ops.gmm(a, b, sizes)
     with pytest.raises(AssertionError):
         ops.gmm_nt(a, b.transpose(1, 2).contiguous(), sizes)
+
+
+# ---- Ring attention (parallel/context.py on one process) ----------------------
+
+
+def ring_run(monkeypatch, device, ring_cls=None):
+    return lambda case: kr.virtual_ring(monkeypatch, case, device, ring_cls)
+
+
+@pytest.mark.parametrize("shape", sorted(set(kr.RING_BLOCK_SHAPES + kr.RING_SHAPES)), ids=str)
+def test_ring_planted_case_is_what_it_says(shape):
+    kr.check_ring_plant(kr.ring_case(*shape))
+
+
+def test_ring_plant_condition_fails_on_the_diagonal_cases():
+    """attn_case keeps every row's dominant key in the row's own chunk: no
+    off-diagonal block of it holds one, which check_ring_plant refuses."""
+    case = kr.attn_case(1, 195, 195, 4, 2, 64)
+    case.update(W=3, S_local=65)
+    with pytest.raises(AssertionError, match="block"):
+        kr.check_ring_plant(case)
+
+
+@pytest.mark.parametrize("shape", kr.RING_SHAPES + [(3, 130, 1, 4, 2, 64)], ids=str)
+def test_virtual_ring_cpu(shape, monkeypatch):
+    """The shipped skip rule, merge and accumulator rotation at W = 2, 3, 4 on
+    the eager branch."""
+    kr.check_ring(ring_run(monkeypatch, "cpu"), kr.ring_case(*shape))
+
+
+def test_virtual_ring_noncausal_cpu(monkeypatch):
+    kr.check_ring(ring_run(monkeypatch, "cpu"), kr.ring_noncausal_case(*kr.RING_NONCAUSAL))
+
+
+def test_virtual_ring_reports_a_failing_rank(monkeypatch):
+    """An exception on one rank ends the ring and is re-raised."""
+    from d9d_amd.parallel import context
+
+    real = context._block_fwd
+
+    def fails_on_the_second_chunk(q, k, v, causal_block, scale):
+        if not causal_block:
+            raise ValueError("planted")
+        return real(q, k, v, causal_block, scale)
+
+    monkeypatch.setattr(context, "_block_fwd", fails_on_the_second_chunk)
+    with pytest.raises(ValueError, match="planted"):
+        kr.virtual_ring(monkeypatch, kr.ring_case(3, 4, 1, 2, 1, 16), "cpu")
+
+
+RING_W3 = (3, 65, 1, 4, 2, 64)
+
+
+@pytest.mark.parametrize("r,j", [(r, j) for r in range(3) for j in range(r + 1)])
+def test_ring_blocks_cpu(r, j):
+    from d9d_amd.parallel import context
+
+    kr.check_ring_block(context._block_fwd, context._block_bwd, _ring_w3_case(), r, j)
+
+
+_RING_W3_CASE = []
+
+
+def _ring_w3_case():
+    if not _RING_W3_CASE:
+        _RING_W3_CASE.append(kr.ring_case(*RING_W3))
+    return _RING_W3_CASE[0]
+
+
+class _RingCopy:
+    """context._RingAttention's two loops, with one fault each behind a flag:
+    the mutants the ring checkers must see. With no flag set it is the shipped
+    algorithm and passes."""
+
+    extra_chunk = False        # skip rule j <= rank + 1
+    acc_stays = False          # K/V rotate, the dK/dV accumulators do not
+
+    @classmethod
+    def _attends(cls, j, rank, causal):
+        return (not causal) or j <= rank + (1 if cls.extra_chunk else 0)
+
+    @classmethod
+    def forward(cls, ctx, q, k, v, group, causal, scale):
+        from d9d_amd.parallel import context
+
+        rank, world = group.rank, group.world
+        B, S, Hq, D = q.shape
+        o = torch.zeros(B, S, Hq, D, dtype=torch.float32, device=q.device)
+        l = torch.full((B, Hq, S), float("-inf"), dtype=torch.float32, device=q.device)
+        cur_k, cur_v = k, v
+        for step in range(world):
+            j = (rank - step) % world
+            if cls._attends(j, rank, causal):
+                o_j, l_j = context._block_fwd(q, cur_k, cur_v, causal and j == rank, scale)
+                l_new = torch.logaddexp(l, l_j)
+                c_old = torch.exp(l - l_new).permute(0, 2, 1).unsqueeze(-1)
+                c_new = torch.exp(l_j - l_new).permute(0, 2, 1).unsqueeze(-1)
+                o, l = o * c_old + o_j.float() * c_new, l_new
+            if step + 1 < world:
+                cur_k, cur_v = context._ring_pass([cur_k, cur_v], group)
+        out = o.to(q.dtype)
+        ctx.save_for_backward(q, k, v, out, l)
+        ctx.group, ctx.causal, ctx.scale = group, causal, scale
+        return out
+
+    @classmethod
+    def backward(cls, ctx, dout):
+        from d9d_amd.parallel import context
+
+        q, k, v, out, lse = ctx.saved_tensors
+        group, causal, scale = ctx.group, ctx.causal, ctx.scale
+        rank, world = group.rank, group.world
+        dq = torch.zeros_like(q, dtype=torch.float32)
+        dk_acc = torch.zeros_like(k, dtype=torch.float32)
+        dv_acc = torch.zeros_like(v, dtype=torch.float32)
+        cur_k, cur_v = k, v
+        for step in range(world):
+            j = (rank - step) % world
+            if cls._attends(j, rank, causal):
+                dq_j, dk_j, dv_j = context._block_bwd(
+                    q, cur_k, cur_v, out, dout, lse, causal and j == rank, scale)
+                dq += dq_j.float()
+                dk_acc += dk_j.float()
+                dv_acc += dv_j.float()
+            if cls.acc_stays:
+                cur_k, cur_v = context._ring_pass([cur_k, cur_v], group)
+            else:
+                cur_k, cur_v, dk_acc, dv_acc = context._ring_pass(
+                    [cur_k, cur_v, dk_acc, dv_acc], group)
+        return dq.to(q.dtype), dk_acc.to(k.dtype), dv_acc.to(v.dtype)
+
+
+def test_ring_checks_see_planted_bugs(monkeypatch):
+    """The checkers themselves. The copy of the shipped loops passes; each of
+    these fails check_ring, and the two _block_bwd faults also fail
+    check_ring_block on an off-diagonal block:
+      * _block_bwd with the chunk's own LSE instead of the merged one;
+      * _block_bwd with delta from the chunk's partial out;
+      * off-diagonal blocks run with the causal mask on;
+      * a ring that also attends to the next chunk (the decoy of a chunk's
+        last row);
+      * a ring that rotates K/V but leaves the dK/dV accumulators behind."""
+    from d9d_amd.parallel import context
+
+    case = _ring_w3_case()
+    fwd, bwd = context._block_fwd, context._block_bwd
+    kr.check_ring(ring_run(monkeypatch, "cpu", _RingCopy), case)
+
+    def own_lse(q, k, v, out_final, dout, lse_merged, causal_block, scale):
+        return bwd(q, k, v, out_final, dout, fwd(q, k, v, causal_block, scale)[1],
+                   causal_block, scale)
+
+    def partial_out_delta(q, k, v, out_final, dout, lse_merged, causal_block, scale):
+        return bwd(q, k, v, fwd(q, k, v, causal_block, scale)[0], dout, lse_merged,
+                   causal_block, scale)
+
+    for mutant, what in ((own_lse, "d[qkv]"), (partial_out_delta, "d[qk]")):
+        with monkeypatch.context() as m:
+            m.setattr(context, "_block_bwd", mutant)
+            with pytest.raises(AssertionError, match=f"ring {what}"):
+                kr.check_ring(ring_run(m, "cpu"), case)
+        with pytest.raises(AssertionError, match=rf"block \(2,0\) {what}"):
+            kr.check_ring_block(fwd, mutant, case, 2, 0)
+
+    with monkeypatch.context() as m:
+        m.setattr(context, "_block_fwd", lambda q, k, v, c, s: fwd(q, k, v, True, s))
+        m.setattr(context, "_block_bwd",
+                  lambda q, k, v, o, do, l, c, s: bwd(q, k, v, o, do, l, True, s))
+        with pytest.raises(AssertionError, match="ring out"):
+            kr.check_ring(ring_run(m, "cpu"), case)
+
+    class ExtraChunk(_RingCopy):
+        extra_chunk = True
+
+    class AccStays(_RingCopy):
+        acc_stays = True
+
+    with pytest.raises(AssertionError, match="ring out"):
+        kr.check_ring(ring_run(monkeypatch, "cpu", ExtraChunk), case)
+    with pytest.raises(AssertionError, match="ring dk"):
+        kr.check_ring(ring_run(monkeypatch, "cpu", AccStays), case)
