@@ -22,8 +22,11 @@
 // dV and delta over DV. Instantiated: DQK = DV in {32, 64, 96, 128} and the
 // one wide pair <192, 128> (MLA: qk 192 / v 128), whose forward takes 64 q
 // rows per workgroup (one m-tile per wave) to stay inside 256 VGPRs and whose
-// backward stages 32 q rows per tile instead of 64 to fit the LDS. The host
-// pads other sizes up to the next pair; qk > 192 or v > 128 is an error.
+// backward stages 32 q rows per tile instead of 64 to fit the LDS. The square
+// pair <256, 256> (both head dims in 193..256) has kernels of its own,
+// flash_fwd256_kernel and flash_bwd256_kernel below. The host pads other
+// sizes up to the next pair; every other pair with qk > 192 or v > 128 is an
+// error.
 #include "common.h"
 #include "mfma.h"
 
@@ -41,17 +44,25 @@ constexpr int kBwdQ = 64;    // backward: q rows per staged Q/dO tile (DQK <= 12
 constexpr int kBwdQWide = 32;  // ... and for the wide pair <192, 128>
 constexpr int kBwdKv = 128;  // backward: kv rows per workgroup (8 waves x 16)
 constexpr int kBwdThreads = 512;
+// the square pair <256, 256> (flash_fwd256_kernel, flash_bwd256_kernel)
+constexpr int kFwd256Waves = 8;               // forward: waves per workgroup
+constexpr int kFwd256Q = kFwd256Waves * 16;   // ... q rows (one m-tile per wave)
+constexpr int kFwd256Kv = 64;                 // ... kv rows per staged K/V tile
+constexpr int kBwd256Q = 32;                  // backward: q rows per staged tile
+constexpr int kBwd256Kv = 64;                 // ... kv rows per workgroup (4 bands x 16)
 constexpr float kLog2e = 1.44269504088896340736f;
 
 // XOR swizzles keep ds_read_b128 bank-conflict-free (guide G4). The XOR moves
 // 16-byte units and must stay inside the LDS row: a mask of m bits needs rows
 // that are a multiple of 16 << m bytes. Row-major [rows][D] tiles (D*2-byte
 // rows) use swz_rm_mask<D>() -- D = 96 has 192-byte rows, a multiple of 64
-// only, so it takes the 2-bit mask, D = 192 (384-byte rows) the 3-bit one;
+// only, so it takes the 2-bit mask, D = 192 (384-byte rows) the 3-bit one,
+// D = 256 (512-byte rows) the 4-bit one;
 // transposed [D][ROWS] tiles use mask 7, or 3 where ROWS = 32 (64-byte rows).
 template <int D>
 constexpr int swz_rm_mask() {
-  constexpr int mask = D == 128 ? 15 : ((D == 64 || D == 192) ? 7 : 3);
+  constexpr int mask =
+      (D == 128 || D == 256) ? 15 : ((D == 64 || D == 192) ? 7 : 3);
   static_assert((D * 2) % (16 * (mask + 1)) == 0, "swizzle leaves its LDS row");
   return mask;
 }
@@ -640,6 +651,286 @@ constexpr size_t fwd_smem_bytes() {
 }
 
 // ---------------------------------------------------------------------------
+// Forward, square pair <256, 256>
+// ---------------------------------------------------------------------------
+
+// Q tile + K tile + V^T tile (flash_fwd256_kernel's LDS carve-up).
+template <int WAVES, int KV>
+constexpr size_t fwd256_smem_bytes() {
+  return sizeof(bf16_t) * (WAVES * 16 * 256 + KV * 256 + 256 * KV);
+}
+
+// At head dim 256 the O accumulator alone is 64 registers per 16 q rows and
+// the Q fragments would be 32 more, so flash_fwd_kernel's layout (Q in
+// registers for the whole kv sweep) does not fit 256 VGPRs. Here every wave
+// owns ONE 16-row m-tile, Q is staged once into LDS and read back as the B
+// fragment of each k-step, and K / V^T tiles of KV rows stream through LDS as
+// in flash_fwd_kernel (same transposed products S^T = K Q^T, O^T = V^T P^T,
+// same pv_pos row order, P stays in registers). WAVES x 16 q rows per
+// workgroup; two waves per SIMD either as one 8-wave workgroup per CU or two
+// 4-wave ones. The epilogue stages O and then its bf16 rounding residual
+// through the Q tile and writes both planes of `out`, (2,B,Sq,Hq,256).
+template <int WAVES, int KV>
+__global__ __launch_bounds__(WAVES * 64, 2) void flash_fwd256_kernel(
+    const bf16_t* __restrict__ q,   // (B,Sq,Hq,256)
+    const bf16_t* __restrict__ k,   // (B,Skv,Hkv,256)
+    const bf16_t* __restrict__ v,   // (B,Skv,Hkv,256)
+    bf16_t* __restrict__ out,       // (2,B,Sq,Hq,256)
+    float* __restrict__ lse,        // (B,Hq,Sq)
+    const float* __restrict__ sinks,  // (Hq,) raw sink logits, or nullptr
+    const int* __restrict__ cu_q,     // (nseq+1,) packed-seq bounds, or nullptr
+    const int* __restrict__ cu_k,
+    const int* __restrict__ qtile_pref,  // (nseq+1,) prefix of ceil(len_q/FQ)
+    int nseq,
+    int B, int Sq, int Skv, int Hq, int Hkv,
+    float scale, int causal, int window_left, int q_offset) {
+  static_assert(KV == 32 || KV == 64, "pv_pos permutes inside 32-row blocks");
+  constexpr int D = 256;
+  constexpr int FQ = WAVES * 16;  // q rows per workgroup
+  constexpr int T = WAVES * 64;   // threads
+  constexpr int kNT = D / 16;     // n-tiles over the v head dim
+  constexpr int kKS = D / 32;     // k-steps over the qk head dim
+  constexpr int kST = KV / 16;    // 16-row score tiles per kv tile
+  static_assert(fwd256_smem_bytes<WAVES, KV>() * (WAVES == 8 ? 1 : 2) <= 163840,
+                "over a CU's LDS");
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* q_lds = smem;                                    // [FQ][D] swizzled
+  bf16_t* k_lds = reinterpret_cast<bf16_t*>(smem) + FQ * D;  // [KV][D], row p = kv pv_pos(p)
+  bf16_t* vt_lds = k_lds + KV * D;                       // [D][KV] transposed
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int lrow = lane & 15;  // the q row (of the wave's m-tile) this lane owns
+  const int lgrp = lane >> 4;
+
+  const TileLoc loc = locate_tile<FQ, false>(
+      cu_q, cu_k, qtile_pref, nseq, Sq, Skv, Hq, q_offset);
+  if (!loc.valid) return;
+  const int b = loc.b, h = loc.h, q_tile = loc.tile, causal_off = loc.causal_off;
+  const int q_lo = loc.q_lo, Sq_loc = loc.Sq_loc, kv_lo = loc.kv_lo, Skv_loc = loc.Skv_loc;
+  const int hkv = h / (Hq / Hkv);
+
+  const int64_t q_base = ((int64_t)b * Sq * Hq + h) * D;
+  const int64_t kv_base = ((int64_t)b * Skv * Hkv + hkv) * D;
+  const int64_t q_row_stride = (int64_t)Hq * D;
+  const int64_t kv_row_stride = (int64_t)Hkv * D;
+
+  const int q_tile_last_row = min(q_tile * FQ + FQ - 1, Sq_loc - 1);
+  int kv_end = Skv_loc;
+  if (causal) kv_end = min(Skv_loc, q_tile_last_row + causal_off + 1);
+  const int num_kv_tiles = (kv_end + KV - 1) / KV;
+  if (num_kv_tiles <= 0) return;
+
+  // ---- stage the q tile once (rows past the sequence repeat its last row) ---
+  for (int idx = threadIdx.x * 8; idx < FQ * D; idx += T * 8) {
+    const int row = idx / D;
+    const int col = idx % D;
+    const int g_row = q_lo + min(q_tile * FQ + row, Sq_loc - 1);
+    *reinterpret_cast<bf16x8*>(swz_rm_at<D>(q_lds, row, col)) =
+        *reinterpret_cast<const bf16x8*>(
+            q + q_base + (int64_t)g_row * q_row_stride + col);
+  }
+
+  // sink and the per-lane l: see flash_fwd_kernel. l is a partial sum over the
+  // kv columns this lane holds, merged over the row's 4 lanes in the epilogue.
+  float m_run = sinks ? sinks[h] : -1e30f;
+  float l_run = (sinks && lgrp == 0) ? 1.f : 0.f;
+  f32x4 o_acc[kNT];  // O^T: lane holds O[q = lrow][d = nt*16 + lgrp*4 + r]
+#pragma unroll
+  for (int nt = 0; nt < kNT; ++nt) o_acc[nt] = {0.f, 0.f, 0.f, 0.f};
+
+  // T14 split staging as in flash_fwd_kernel
+  constexpr int kKIters = (KV * D) / (T * 8);
+  constexpr int kVIters = (KV / 4) * (D / 2) / T;
+  static_assert(kKIters * T * 8 == KV * D && kVIters * T == (KV / 4) * (D / 2),
+                "staging covers the tiles");
+  bf16x8 k_reg[kKIters];
+  bf16x4_bits v_c0[kVIters], v_c1[kVIters];
+
+  auto load_regs = [&](int kt) {
+    const int kv0 = kt * KV;
+#pragma unroll
+    for (int it = 0; it < kKIters; ++it) {
+      const int idx = (threadIdx.x + it * T) * 8;
+      const int g_row = kv_lo + min(kv0 + pv_pos(idx / D), Skv_loc - 1);
+      k_reg[it] = *reinterpret_cast<const bf16x8*>(
+          k + kv_base + (int64_t)g_row * kv_row_stride + idx % D);
+    }
+#pragma unroll
+    for (int it = 0; it < kVIters; ++it) {
+      load_transposed_block<D>(v_c0[it], v_c1[it], v + kv_base, kv_row_stride,
+                               kv_lo, kv0, Skv_loc - 1, threadIdx.x + it * T);
+    }
+  };
+  auto store_lds = [&]() {
+#pragma unroll
+    for (int it = 0; it < kKIters; ++it) {
+      const int idx = (threadIdx.x + it * T) * 8;
+      *reinterpret_cast<bf16x8*>(
+          swz_rm_at<D>(reinterpret_cast<char*>(k_lds), idx / D, idx % D)) = k_reg[it];
+    }
+#pragma unroll
+    for (int it = 0; it < kVIters; ++it) {
+      store_transposed_block<D, KV>(vt_lds, v_c0[it], v_c1[it], threadIdx.x + it * T);
+    }
+  };
+
+  load_regs(0);
+  store_lds();
+  __syncthreads();  // also publishes the q tile
+
+  const int q_row0 = q_tile * FQ + wave * 16;  // this wave's first q row
+  for (int kt = 0; kt < num_kv_tiles; ++kt) {
+    const int kv0 = kt * KV;
+    if (kt + 1 < num_kv_tiles) load_regs(kt + 1);  // issue early
+
+    // ---- S^T = K Q^T: one Q fragment per k-step, read from LDS --------------
+    // lane holds S[q = lrow][kv = kv0 + pv_pos(nt*16 + lgrp*4 + r)] in st[nt][r]
+    f32x4 st[kST];
+#pragma unroll
+    for (int nt = 0; nt < kST; ++nt) st[nt] = {0.f, 0.f, 0.f, 0.f};
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < kKS; ++ks) {
+      const int d0 = ks * 32 + lgrp * 8;
+      const bf16x8 qb = *reinterpret_cast<const bf16x8*>(
+          swz_rm_at<D>(q_lds, wave * 16 + lrow, d0));
+#pragma unroll
+      for (int nt = 0; nt < kST; ++nt) {
+        const bf16x8 ka = *reinterpret_cast<const bf16x8*>(
+            swz_rm_at<D>(reinterpret_cast<char*>(k_lds), nt * 16 + lrow, d0));
+        st[nt] = mfma16(ka, qb, st[nt]);
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+
+    // ---- per-lane online softmax; P^T packed as PV's B operand -------------
+    // tile-level mask skip: the per-element chain runs on edge tiles only
+    const int row_lo = q_row0 + causal_off;
+    const bool any_mask =
+        (kv0 + KV > kv_end) ||
+        (causal && kv0 + KV - 1 > row_lo) ||
+        (window_left >= 0 && kv0 < row_lo + 15 - window_left);
+    if (any_mask) {
+      const int row = row_lo + lrow;
+#pragma unroll
+      for (int nt = 0; nt < kST; ++nt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int col = kv0 + pv_pos(nt * 16 + lgrp * 4 + r);
+          const bool masked = causal_window_masked(
+              col >= kv_end, row, col, causal, window_left);
+          st[nt][r] = masked ? -1e30f : st[nt][r] * scale;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int nt = 0; nt < kST; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st[nt][r] = st[nt][r] * scale;
+    }
+    float mx = st[0][0];
+#pragma unroll
+    for (int nt = 0; nt < kST; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[nt][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    float l_add = 0.f;
+#pragma unroll
+    for (int nt = 0; nt < kST; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        st[nt][r] = __builtin_amdgcn_exp2f((st[nt][r] - m_new) * kLog2e);
+        l_add += st[nt][r];
+      }
+    // lazy rescale (wave-uniform branch), see flash_fwd_kernel
+    if (__all(m_new == m_run)) {
+      l_run += l_add;
+    } else {
+      const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * kLog2e);
+      l_run = l_run * alpha + l_add;
+      m_run = m_new;
+#pragma unroll
+      for (int nt = 0; nt < kNT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o_acc[nt][r] *= alpha;
+    }
+    // B slot (lgrp, j) of PV k-step ks2 takes kv = 32 ks2 + 8 lgrp + j: the
+    // registers of st[2 ks2] then st[2 ks2 + 1] (see pv_pos)
+    bf16x8 pb[KV / 32];
+#pragma unroll
+    for (int ks2 = 0; ks2 < KV / 32; ++ks2)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        pb[ks2][j] = (bf16_t)st[2 * ks2][j];
+        pb[ks2][4 + j] = (bf16_t)st[2 * ks2 + 1][j];
+      }
+
+    // ---- O^T += V^T P^T ------------------------------------------------------
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks2 = 0; ks2 < KV / 32; ++ks2) {
+      const int kv_off = ks2 * 32 + lgrp * 8;
+#pragma unroll
+      for (int nt = 0; nt < kNT; ++nt) {
+        const bf16x8 va = *reinterpret_cast<const bf16x8*>(
+            swz_t_at<KV>(reinterpret_cast<char*>(vt_lds), nt * 16 + lrow, kv_off));
+        o_acc[nt] = mfma16(va, pb[ks2], o_acc[nt]);
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+
+    __syncthreads();
+    if (kt + 1 < num_kv_tiles) {
+      store_lds();
+      __syncthreads();
+    }
+  }
+
+  // ---- epilogue: merge l over the row's 4 lanes; O /= l; both planes of out
+  // go through the Q tile (same [FQ][D] shape) for coalesced 16B stores; LSE --
+  l_run += __shfl_xor(l_run, 32, 64);
+  l_run += __shfl_xor(l_run, 16, 64);
+  const float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
+#pragma unroll
+  for (int plane = 0; plane < 2; ++plane) {
+    if (plane == 1) __syncthreads();  // plane 0 has been read out
+#pragma unroll
+    for (int nt = 0; nt < kNT; ++nt) {
+      bf16x4_bits o4;  // 4 consecutive d of one row
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float o = o_acc[nt][r] * inv_l;
+        // plane 1: the bf16 rounding residual O - bf16(O), for delta
+        o4.s[r] = bf16_bits(plane == 0 ? (bf16_t)o : (bf16_t)(o - (float)(bf16_t)o));
+      }
+      *reinterpret_cast<uint64_t*>(
+          swz_rm_at<D>(q_lds, wave * 16 + lrow, nt * 16 + lgrp * 4)) = o4.u;
+    }
+    __syncthreads();
+    bf16_t* dst = out + (int64_t)plane * B * Sq * Hq * D;
+    for (int idx = threadIdx.x * 8; idx < FQ * D; idx += T * 8) {
+      const int row = idx / D;
+      const int col = idx % D;
+      const int rg = q_tile * FQ + row;
+      if (rg < Sq_loc) {
+        *reinterpret_cast<bf16x8*>(
+            dst + q_base + (int64_t)(q_lo + rg) * q_row_stride + col) =
+            *reinterpret_cast<const bf16x8*>(swz_rm_at<D>(q_lds, row, col));
+      }
+    }
+  }
+  if (lgrp == 0 && q_row0 + lrow < Sq_loc) {
+    // regular: (B,Hq,Sq); varlen: (Hq,total) with b == 0
+    lse[((int64_t)b * Hq + h) * Sq + q_lo + q_row0 + lrow] =
+        m_run + __logf(fmaxf(l_run, 1e-30f));
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Backward
 // ---------------------------------------------------------------------------
 
@@ -1096,6 +1387,312 @@ __global__ __launch_bounds__(512, 1) void flash_bwd_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Backward, square pair <256, 256>
+// ---------------------------------------------------------------------------
+
+// P / dS images of flash_bwd256_kernel: kBwd256Kv / 16 blocks of 128 B per
+// 4-q row, stride padded +32 B.
+constexpr int kBwd256XStride = (kBwd256Kv / 16) * 128 + 32;
+
+// Q, dO, dO^T, Q^T tiles (kBwd256Q rows of 256) + K^T + the P and dS images.
+constexpr size_t bwd256_smem_bytes() {
+  return sizeof(bf16_t) * (4 * kBwd256Q * 256 + 256 * kBwd256Kv) +
+         2 * (kBwd256Q / 4) * kBwd256XStride;
+}
+static_assert(bwd256_smem_bytes() <= 163840, "over a workgroup's LDS");
+
+// flash_bwd_kernel's geometry (8 waves x 16 kv rows, dK and dV of a full row
+// in registers) needs 128 accumulator + 64 fragment VGPRs at head dim 256 and
+// 145 KB of LDS. This kernel keeps its FA2 decomposition, the P / dS tr16
+// block images and the two-barrier q-tile loop, and splits the work
+// differently: a workgroup owns 64 kv rows, its 8 waves are (band, r) = (wave
+// >> 1, wave & 1) with band a 16-row kv band.
+//   * scores: wave (band, r) computes S^T and dP^T of its band against q
+//     m-tile r of the 32-row q tile over the whole head dim (8 + 8 MFMAs) and
+//     writes that part of the images; no MFMA is done twice.
+//   * dV / dK: wave (band, r) owns head-dim columns r*128 .. r*128+127 of its
+//     band's dV and dK over all 32 q rows (8 + 8 n-tiles, 64 accumulator
+//     VGPRs). P and dS pass through LDS anyway, so a wave may consume q rows
+//     whose scores its partner produced.
+//   * dQ: m-tile wave & 1, n-tiles (wave >> 1) * 4 .. + 3, two k-steps over
+//     the 64 kv rows; fp32 global atomics.
+// The band's K and V fragments stay in registers (64 VGPRs).
+__global__ __launch_bounds__(512, 1) void flash_bwd256_kernel(
+    const bf16_t* __restrict__ q,
+    const bf16_t* __restrict__ k,
+    const bf16_t* __restrict__ v,
+    const bf16_t* __restrict__ dout,
+    const float* __restrict__ lse,    // (B,Hq,Sq)
+    const float* __restrict__ delta,  // (B,Hq,Sq)
+    float* __restrict__ dq,           // (B,Sq,Hq,256) fp32 accum
+    float* __restrict__ dk,           // (B,Skv,Hkv,256) fp32 accum
+    float* __restrict__ dv,           // (B,Skv,Hkv,256) fp32 accum
+    const int* __restrict__ cu_q,     // packed-seq bounds, or nullptr
+    const int* __restrict__ cu_k,
+    const int* __restrict__ kvtile_pref,  // prefix of ceil(len_k/kBwd256Kv)
+    int nseq,
+    int B, int Sq, int Skv, int Hq, int Hkv,
+    float scale, int causal, int window_left, int q_offset) {
+  constexpr int D = 256;
+  constexpr int QR = kBwd256Q;
+  constexpr int KVT = kBwd256Kv;
+  constexpr int kKS = D / 32;    // k-steps over the head dim (S^T, dP^T)
+  constexpr int kNTW = D / 32;   // n-tiles of a wave's half of the head dim (dV, dK)
+  constexpr int kNTQ = D / 64;   // n-tiles of a wave's quarter of the head dim (dQ)
+  constexpr int kXqStride = kBwd256XStride;
+  static_assert(QR == 32 && KVT == 64 && kBwdThreads == 512,
+                "8 waves = 4 kv bands x 2 q m-tiles");
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // bwd256_smem_bytes() is this carve-up; the buffers play the parts they
+  // play in flash_bwd_kernel
+  bf16_t* q_lds = reinterpret_cast<bf16_t*>(smem);   // [QR][D] swizzled rows
+  bf16_t* do_lds = q_lds + QR * D;                   // [QR][D]
+  bf16_t* tdo_lds = do_lds + QR * D;                 // [D][QR]: dO^T
+  bf16_t* tq_lds = tdo_lds + D * QR;                 // [D][QR]: Q^T
+  bf16_t* kt_lds = tq_lds + D * QR;                  // [D][KVT]: K^T
+  char* x1_lds = reinterpret_cast<char*>(kt_lds + D * KVT);  // P image
+  char* x2_lds = x1_lds + (QR / 4) * kXqStride;              // dS image
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int lrow = lane & 15;
+  const int lgrp = lane >> 4;
+  const int band = wave >> 1;  // 16-row kv band of the 64-row tile
+  const int role = wave & 1;   // q m-tile (scores, dQ) and head-dim half (dV, dK)
+
+  const TileLoc loc = locate_tile<KVT, true>(
+      cu_q, cu_k, kvtile_pref, nseq, Sq, Skv, Hq, q_offset);
+  if (!loc.valid || loc.Sq_loc <= 0) return;
+  const int b = loc.b, h = loc.h, kv_tile = loc.tile, causal_off = loc.causal_off;
+  const int q_lo = loc.q_lo, Sq_loc = loc.Sq_loc, kv_lo = loc.kv_lo, Skv_loc = loc.Skv_loc;
+  const int hkv = h / (Hq / Hkv);
+
+  const int64_t q_base = ((int64_t)b * Sq * Hq + h) * D;
+  const int64_t kv_base = ((int64_t)b * Skv * Hkv + hkv) * D;
+  const int64_t q_row_stride = (int64_t)Hq * D;
+  const int64_t kv_row_stride = (int64_t)Hkv * D;
+  const float* lse_row = lse + ((int64_t)b * Hq + h) * Sq + q_lo;
+  const float* delta_row = delta + ((int64_t)b * Hq + h) * Sq + q_lo;
+
+  const int kv0 = kv_tile * KVT;
+
+  // The band's 16 kv rows: K and V A-fragments in registers (both waves of a
+  // band hold the same ones).
+  bf16x8 k_frag[kKS], v_frag[kKS];
+  {
+    const int kv_row_global = kv_lo + min(kv0 + band * 16 + lrow, Skv_loc - 1);
+    const bf16_t* kp = k + kv_base + (int64_t)kv_row_global * kv_row_stride;
+    const bf16_t* vp = v + kv_base + (int64_t)kv_row_global * kv_row_stride;
+#pragma unroll
+    for (int ks = 0; ks < kKS; ++ks) {
+      k_frag[ks] = *reinterpret_cast<const bf16x8*>(kp + ks * 32 + lgrp * 8);
+      v_frag[ks] = *reinterpret_cast<const bf16x8*>(vp + ks * 32 + lgrp * 8);
+    }
+  }
+
+  // Stage K^T once (for dQ's B fragments).
+  stage_transposed_tile<D, KVT, kBwdThreads>(
+      kt_lds, k + kv_base, kv_row_stride, kv_lo, kv0, Skv_loc - 1, threadIdx.x);
+
+  f32x4 dk_acc[kNTW], dv_acc[kNTW];
+#pragma unroll
+  for (int nt = 0; nt < kNTW; ++nt) {
+    dk_acc[nt] = {0.f, 0.f, 0.f, 0.f};
+    dv_acc[nt] = {0.f, 0.f, 0.f, 0.f};
+  }
+
+  int q_start = 0;
+  if (causal) {
+    // first q tile whose last aligned position reaches kv0
+    q_start = (max(kv0 - causal_off, 0) / QR) * QR;
+  }
+  if (q_start >= Sq_loc) return;
+
+  // T14 prefetch of the next q tile's Q / dO rows, as in flash_bwd_kernel
+  constexpr int kQRegs = QR * D / (kBwdThreads * 8);
+  static_assert(kQRegs * kBwdThreads * 8 == QR * D, "staging covers the tile");
+  bf16x8 q_reg[kQRegs], do_reg[kQRegs];
+
+  auto load_qdo_regs = [&](int qt_next) {
+#pragma unroll
+    for (int it = 0; it < kQRegs; ++it) {
+      const int idx = (threadIdx.x + it * kBwdThreads) * 8;
+      const int g_row = q_lo + min(qt_next + idx / D, Sq_loc - 1);
+      const int64_t off = q_base + (int64_t)g_row * q_row_stride + idx % D;
+      q_reg[it] = *reinterpret_cast<const bf16x8*>(q + off);
+      do_reg[it] = *reinterpret_cast<const bf16x8*>(dout + off);
+    }
+  };
+  auto store_qdo_lds = [&]() {
+#pragma unroll
+    for (int it = 0; it < kQRegs; ++it) {
+      const int idx = (threadIdx.x + it * kBwdThreads) * 8;
+      *reinterpret_cast<bf16x8*>(swz_rm_at<D>(
+          reinterpret_cast<char*>(q_lds), idx / D, idx % D)) = q_reg[it];
+      *reinterpret_cast<bf16x8*>(swz_rm_at<D>(
+          reinterpret_cast<char*>(do_lds), idx / D, idx % D)) = do_reg[it];
+    }
+  };
+
+  load_qdo_regs(q_start);
+  store_qdo_lds();
+  __syncthreads();
+
+  for (int qt = q_start; qt < Sq_loc; qt += QR) {
+    if (qt + QR < Sq_loc) load_qdo_regs(qt + QR);  // issue early
+    // dO^T and Q^T images; first read after the x-stage barrier below
+    transpose_lds_tile<D, QR, kBwdThreads>(tdo_lds, do_lds, threadIdx.x);
+    transpose_lds_tile<D, QR, kBwdThreads>(tq_lds, q_lds, threadIdx.x);
+
+    // ---- S^T = K Q^T and dP^T = V dO^T: band's 16 kv x m-tile `role` -------
+    // lane holds (kv = band*16 + lgrp*4 + r, q = role*16 + lrow) in register r
+    f32x4 st_acc = {0.f, 0.f, 0.f, 0.f}, dpt_acc = {0.f, 0.f, 0.f, 0.f};
+    const int q_l = role * 16 + lrow;
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < kKS; ++ks) {
+      const int d0 = ks * 32 + lgrp * 8;
+      const bf16x8 qb = *reinterpret_cast<const bf16x8*>(
+          swz_rm_at<D>(reinterpret_cast<char*>(q_lds), q_l, d0));
+      st_acc = mfma16(k_frag[ks], qb, st_acc);
+    }
+#pragma unroll
+    for (int ks = 0; ks < kKS; ++ks) {
+      const int d0 = ks * 32 + lgrp * 8;
+      const bf16x8 db = *reinterpret_cast<const bf16x8*>(
+          swz_rm_at<D>(reinterpret_cast<char*>(do_lds), q_l, d0));
+      dpt_acc = mfma16(v_frag[ks], db, dpt_acc);
+    }
+    __builtin_amdgcn_s_setprio(0);
+
+    // ---- P^T = exp(S^T * scale - lse[q]), masked entries 0;
+    //      dS^T = P^T * (dP^T - delta[q]) * scale ------------------------------
+    // tile-level mask skip as in flash_bwd_kernel
+    const bool any_mask =
+        (kv0 + KVT > Skv_loc) || (qt + QR > Sq_loc) ||
+        (causal && kv0 + KVT - 1 > qt + causal_off) ||
+        (window_left >= 0 && kv0 < qt + QR - 1 + causal_off - window_left);
+    const int q_glob = qt + q_l;
+    // clamped: edge tiles would read past the lse / delta rows
+    const float l = lse_row[min(q_glob, Sq_loc - 1)];
+    const float dlt = delta_row[min(q_glob, Sq_loc - 1)];
+    bf16x4_bits p4, d4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float p = __builtin_amdgcn_exp2f((st_acc[r] * scale - l) * kLog2e);
+      if (any_mask) {
+        const int kv_glob = kv0 + band * 16 + lgrp * 4 + r;
+        const bool masked = causal_window_masked(
+            (kv_glob >= Skv_loc) || (q_glob >= Sq_loc), q_glob + causal_off,
+            kv_glob, causal, window_left);
+        p = masked ? 0.f : p;
+      }
+      p4.s[r] = bf16_bits((bf16_t)p);
+      d4.s[r] = bf16_bits((bf16_t)(p * (dpt_acc[r] - dlt) * scale));
+    }
+
+    // ---- stage P and dS into the blocked images, ONE barrier --------------
+    // value (q, kv) at qb = q>>2 row, block kv>>4, inner (q&3)*32 + (kv&15)*2
+    {
+      const size_t byte = (size_t)(q_l >> 2) * kXqStride + band * 128 +
+                          (q_l & 3) * 32 + lgrp * 8;
+      *reinterpret_cast<uint64_t*>(x1_lds + byte) = p4.u;
+      *reinterpret_cast<uint64_t*>(x2_lds + byte) = d4.u;
+    }
+    __syncthreads();
+
+    // ---- dV += P^T dO; dK += dS^T Q over this wave's half of the head dim --
+    {
+      // A fragment (m = kv row band*16 + lrow, k = 8 q at q_off) = two
+      // ds_read_b64_tr_b16 of the [4 q][16 kv] blocks (qb, band)
+      const int q_off = lgrp * 8;
+      auto xfrag = [&](const char* img) -> bf16x8 {
+        const size_t b0 = (size_t)(q_off >> 2) * kXqStride + band * 128 + lrow * 8;
+        bf16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+            (__attribute__((address_space(3))) bf16x4*)(img + b0));
+        bf16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+            (__attribute__((address_space(3))) bf16x4*)(img + b0 + kXqStride));
+        bf16x8 f;
+#pragma unroll
+        for (int t2 = 0; t2 < 4; ++t2) { f[t2] = lo4[t2]; f[4 + t2] = hi4[t2]; }
+        return f;
+      };
+      const bf16x8 pa = xfrag(x1_lds);
+      const bf16x8 da = xfrag(x2_lds);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int nt = 0; nt < kNTW; ++nt) {
+        const int d = (role * kNTW + nt) * 16 + lrow;
+        const bf16x8 dob = *reinterpret_cast<const bf16x8*>(
+            swz_t_at<QR>(reinterpret_cast<char*>(tdo_lds), d, q_off));
+        const bf16x8 qb = *reinterpret_cast<const bf16x8*>(
+            swz_t_at<QR>(reinterpret_cast<char*>(tq_lds), d, q_off));
+        dv_acc[nt] = mfma16(pa, dob, dv_acc[nt]);
+        dk_acc[nt] = mfma16(da, qb, dk_acc[nt]);
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+
+    // ---- dQ partial = dS K: m-tile `role`, head-dim quarter `band` ----------
+    {
+      f32x4 dq_acc[kNTQ];
+#pragma unroll
+      for (int nt = 0; nt < kNTQ; ++nt) dq_acc[nt] = {0.f, 0.f, 0.f, 0.f};
+      const size_t qbase = (size_t)(q_l >> 2) * kXqStride + (q_l & 3) * 32;
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int ks2 = 0; ks2 < KVT / 32; ++ks2) {
+        const int kv_off = ks2 * 32 + lgrp * 8;
+        const bf16x8 da = *reinterpret_cast<const bf16x8*>(
+            x2_lds + qbase + (kv_off >> 4) * 128 + (kv_off & 15) * 2);
+#pragma unroll
+        for (int nt = 0; nt < kNTQ; ++nt) {
+          const int d = (band * kNTQ + nt) * 16 + lrow;
+          const bf16x8 kb = *reinterpret_cast<const bf16x8*>(
+              swz_t_at<KVT>(reinterpret_cast<char*>(kt_lds), d, kv_off));
+          dq_acc[nt] = mfma16(da, kb, dq_acc[nt]);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int qg = qt + role * 16 + lgrp * 4 + r;
+        if (qg < Sq_loc) {
+#pragma unroll
+          for (int nt = 0; nt < kNTQ; ++nt) {
+            atomicAdd(dq + q_base + (int64_t)(q_lo + qg) * q_row_stride +
+                          (band * kNTQ + nt) * 16 + lrow,
+                      dq_acc[nt][r]);
+          }
+        }
+      }
+    }
+    // nothing above reads q_lds / do_lds after the x-stage barrier, so the
+    // store only needs the end-of-iteration barrier (see flash_bwd_kernel)
+    if (qt + QR < Sq_loc) {
+      store_qdo_lds();
+    }
+    __syncthreads();
+  }
+
+  // ---- flush dK, dV (atomicAdd: GQA groups and padded tiles overlap) -------
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int kv_glob = kv0 + band * 16 + lgrp * 4 + r;
+    if (kv_glob < Skv_loc) {
+      const int64_t row = kv_base + (int64_t)(kv_lo + kv_glob) * kv_row_stride;
+#pragma unroll
+      for (int nt = 0; nt < kNTW; ++nt) {
+        const int d = (role * kNTW + nt) * 16 + lrow;
+        atomicAdd(dk + row + d, dk_acc[nt][r]);
+        atomicAdd(dv + row + d, dv_acc[nt][r]);
+      }
+    }
+  }
+}
+
 // MFMA fragment-map self-check: C = A@B for one 16x32 @ 32x16 tile.
 __global__ void mfma_selfcheck_kernel(
     const bf16_t* __restrict__ a,  // (16, 32) row-major
@@ -1200,7 +1797,9 @@ __global__ void cast3_f32_bf16_kernel(
 namespace {
 
 // The instantiated <DQK, DV> pair a (qk, v) head-dim pair is padded to: one
-// common D in {32, 64, 96, 128} while both fit, else the wide pair.
+// common D in {32, 64, 96, 128} while both fit, else the wide pair <192, 128>
+// while both fit that, else the square pair <256, 256>, which takes exactly
+// the pairs with both dims in 193..256.
 struct HeadDims {
   int qk, v;
 };
@@ -1210,10 +1809,22 @@ HeadDims padded_head_dims(int d_qk, int d_v) {
   for (int cand : {32, 64, 96, 128}) {
     if (d <= cand) return {cand, cand};
   }
-  TORCH_CHECK(d_qk <= 192 && d_v <= 128,
+  if (d_qk <= 192 && d_v <= 128) return {192, 128};
+  TORCH_CHECK(std::min(d_qk, d_v) > 192 && d <= 256,
               "flash attention supports qk head_dim <= 192 with v head_dim <= "
-              "128; got qk ", d_qk, ", v ", d_v);
-  return {192, 128};
+              "128, or qk and v head_dim both in 193..256; got qk ", d_qk,
+              ", v ", d_v);
+  return {256, 256};
+}
+
+// Per-route tile sizes: the forward's q rows and the backward's kv rows per
+// workgroup, which size the grids and prepare_varlen's tile prefix.
+int fwd_q_rows(HeadDims pad) {
+  return pad.qk == 256 ? d9d::kFwd256Q : pad.qk > 128 ? d9d::kFwdQWide : d9d::kFwdQ;
+}
+
+int bwd_kv_rows(HeadDims pad) {
+  return pad.qk == 256 ? d9d::kBwd256Kv : d9d::kBwdKv;
 }
 
 torch::Tensor maybe_pad_d(torch::Tensor t, int D_pad) {
@@ -1333,6 +1944,7 @@ void dispatch_head_dims(HeadDims d, F&& f) {
     case 96: f(integral_constant<int, 96>{}, integral_constant<int, 96>{}); break;
     case 128: f(integral_constant<int, 128>{}, integral_constant<int, 128>{}); break;
     case 192: f(integral_constant<int, 192>{}, integral_constant<int, 128>{}); break;
+    case 256: f(integral_constant<int, 256>{}, integral_constant<int, 256>{}); break;
   }
 }
 
@@ -1366,7 +1978,7 @@ std::vector<torch::Tensor> flash_attn_fwd(
   }
 
   const HeadDims pad = padded_head_dims(D, Dv);
-  const int fq = pad.qk > 128 ? d9d::kFwdQWide : d9d::kFwdQ;  // q rows per workgroup
+  const int fq = fwd_q_rows(pad);
   const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, Sq, Skv, fq,
                                        /*tile_kv=*/false, q.device(), fn);
 
@@ -1374,7 +1986,8 @@ std::vector<torch::Tensor> flash_attn_fwd(
   auto kp = maybe_pad_d(k, pad.qk);
   auto vp = maybe_pad_d(v, pad.v);
 
-  // the wide pair writes a second plane: O's bf16 rounding residual
+  // the wide and the square-256 pair write a second plane: O's bf16 rounding
+  // residual
   const bool wide = pad.qk > 128;
   auto out2 = wide ? torch::empty({2, B, Sq, Hq, (int64_t)pad.v}, qp.options())
                    : torch::empty({B, Sq, Hq, (int64_t)pad.v}, qp.options());
@@ -1394,17 +2007,31 @@ std::vector<torch::Tensor> flash_attn_fwd(
 
   dispatch_head_dims(pad, [&](auto dqk, auto dv) {
     constexpr int DQK = decltype(dqk)::value, DV = decltype(dv)::value;
-    constexpr int FQ = DQK > 128 ? d9d::kFwdQWide : d9d::kFwdQ;
-    hipLaunchKernelGGL((d9d::flash_fwd_kernel<DQK, DV, FQ>), grid, dim3(256),
-                       (d9d::fwd_smem_bytes<DQK, DV>()), stream,
-                       reinterpret_cast<const __bf16*>(qp.data_ptr()),
-                       reinterpret_cast<const __bf16*>(kp.data_ptr()),
-                       reinterpret_cast<const __bf16*>(vp.data_ptr()),
-                       reinterpret_cast<__bf16*>(out2.data_ptr()),
-                       lse.data_ptr<float>(), sinks_ptr, vl.cu_q_ptr,
-                       vl.cu_k_ptr, vl.pref_ptr, vl.nseq, B, Sq, Skv, Hq, Hkv,
-                       (float)softmax_scale, causal ? 1 : 0, (int)window_left,
-                       (int)q_offset);
+    if constexpr (DQK == 256) {
+      constexpr int W = d9d::kFwd256Waves, KV = d9d::kFwd256Kv;
+      hipLaunchKernelGGL((d9d::flash_fwd256_kernel<W, KV>), grid, dim3(W * 64),
+                         (d9d::fwd256_smem_bytes<W, KV>()), stream,
+                         reinterpret_cast<const __bf16*>(qp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(kp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(vp.data_ptr()),
+                         reinterpret_cast<__bf16*>(out2.data_ptr()),
+                         lse.data_ptr<float>(), sinks_ptr, vl.cu_q_ptr,
+                         vl.cu_k_ptr, vl.pref_ptr, vl.nseq, B, Sq, Skv, Hq, Hkv,
+                         (float)softmax_scale, causal ? 1 : 0, (int)window_left,
+                         (int)q_offset);
+    } else {
+      constexpr int FQ = DQK > 128 ? d9d::kFwdQWide : d9d::kFwdQ;
+      hipLaunchKernelGGL((d9d::flash_fwd_kernel<DQK, DV, FQ>), grid, dim3(256),
+                         (d9d::fwd_smem_bytes<DQK, DV>()), stream,
+                         reinterpret_cast<const __bf16*>(qp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(kp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(vp.data_ptr()),
+                         reinterpret_cast<__bf16*>(out2.data_ptr()),
+                         lse.data_ptr<float>(), sinks_ptr, vl.cu_q_ptr,
+                         vl.cu_k_ptr, vl.pref_ptr, vl.nseq, B, Sq, Skv, Hq, Hkv,
+                         (float)softmax_scale, causal ? 1 : 0, (int)window_left,
+                         (int)q_offset);
+    }
   });
 
   if (pad.v != Dv) out = out.narrow(-1, 0, Dv).contiguous();
@@ -1475,8 +2102,9 @@ std::vector<torch::Tensor> flash_attn_bwd(
   }
   const HeadDims pad = padded_head_dims(D, Dv);
 
+  const int kvt = bwd_kv_rows(pad);
   const VarlenMeta vl = prepare_varlen(cu_seqlens_q, cu_seqlens_k, Sq, Skv,
-                                       d9d::kBwdKv, /*tile_kv=*/true, q.device(), fn);
+                                       kvt, /*tile_kv=*/true, q.device(), fn);
 
   auto qp = maybe_pad_d(q, pad.qk);
   auto kp = maybe_pad_d(k, pad.qk);
@@ -1519,25 +2147,40 @@ std::vector<torch::Tensor> flash_attn_bwd(
     delta.sub_(dlse_f.to(torch::kFloat32));
   }
 
-  const dim3 grid(varlen ? vl.n_tiles : (Skv + d9d::kBwdKv - 1) / d9d::kBwdKv,
+  const dim3 grid(varlen ? vl.n_tiles : (Skv + kvt - 1) / kvt,
                   varlen ? Hq : B * Hq);
   dispatch_head_dims(pad, [&](auto dqk, auto dv_c) {
     constexpr int DQK = decltype(dqk)::value, DV = decltype(dv_c)::value;
-    constexpr int QR = DQK > 128 ? d9d::kBwdQWide : d9d::kBwdQ;
-    constexpr size_t smem = d9d::bwd_smem_bytes<DQK, DV, QR>();
-    static_assert(smem <= 160 * 1024, "over a workgroup's LDS");
-    hipLaunchKernelGGL((d9d::flash_bwd_kernel<DQK, DV, QR>), grid,
-                       dim3(d9d::kBwdThreads), smem, stream,
-                       reinterpret_cast<const __bf16*>(qp.data_ptr()),
-                       reinterpret_cast<const __bf16*>(kp.data_ptr()),
-                       reinterpret_cast<const __bf16*>(vp.data_ptr()),
-                       reinterpret_cast<const __bf16*>(dop.data_ptr()),
-                       lse.data_ptr<float>(), delta.data_ptr<float>(),
-                       dq32.data_ptr<float>(), dk32.data_ptr<float>(),
-                       dv32.data_ptr<float>(), vl.cu_q_ptr, vl.cu_k_ptr,
-                       vl.pref_ptr, vl.nseq, B, Sq, Skv, Hq, Hkv,
-                       (float)softmax_scale, causal ? 1 : 0, (int)window_left,
-                       (int)q_offset);
+    if constexpr (DQK == 256) {
+      hipLaunchKernelGGL(d9d::flash_bwd256_kernel, grid,
+                         dim3(d9d::kBwdThreads), d9d::bwd256_smem_bytes(), stream,
+                         reinterpret_cast<const __bf16*>(qp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(kp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(vp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(dop.data_ptr()),
+                         lse.data_ptr<float>(), delta.data_ptr<float>(),
+                         dq32.data_ptr<float>(), dk32.data_ptr<float>(),
+                         dv32.data_ptr<float>(), vl.cu_q_ptr, vl.cu_k_ptr,
+                         vl.pref_ptr, vl.nseq, B, Sq, Skv, Hq, Hkv,
+                         (float)softmax_scale, causal ? 1 : 0, (int)window_left,
+                         (int)q_offset);
+    } else {
+      constexpr int QR = DQK > 128 ? d9d::kBwdQWide : d9d::kBwdQ;
+      constexpr size_t smem = d9d::bwd_smem_bytes<DQK, DV, QR>();
+      static_assert(smem <= 160 * 1024, "over a workgroup's LDS");
+      hipLaunchKernelGGL((d9d::flash_bwd_kernel<DQK, DV, QR>), grid,
+                         dim3(d9d::kBwdThreads), smem, stream,
+                         reinterpret_cast<const __bf16*>(qp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(kp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(vp.data_ptr()),
+                         reinterpret_cast<const __bf16*>(dop.data_ptr()),
+                         lse.data_ptr<float>(), delta.data_ptr<float>(),
+                         dq32.data_ptr<float>(), dk32.data_ptr<float>(),
+                         dv32.data_ptr<float>(), vl.cu_q_ptr, vl.cu_k_ptr,
+                         vl.pref_ptr, vl.nseq, B, Sq, Skv, Hq, Hkv,
+                         (float)softmax_scale, causal ? 1 : 0, (int)window_left,
+                         (int)q_offset);
+    }
   });
 
   torch::Tensor dq, dk, dv;

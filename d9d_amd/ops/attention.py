@@ -10,7 +10,9 @@ Layout: q (B, S, Hq, Dqk), k (B, S, Hkv, Dqk), v (B, S, Hkv, Dv),
 out (B, S, Hq, Dv), lse (B, Hq, S) natural-log-sum-exp of the scores row.
 GPU head dims: Dqk and Dv up to 128 each (the narrower side is zero-padded to
 the wider), or Dqk up to 192 with Dv up to 128 (the kernels' <192, 128> pair,
-MLA's default shape); anything wider raises ValueError before any launch.
+MLA's default shape), or Dqk and Dv both in 193..256 (the <256, 256> kernels,
+the full-attention layers of hybrid models); any other pair raises ValueError
+before any launch.
 """
 
 import math
@@ -77,6 +79,9 @@ _MAX_SQUARE_HEAD_DIM = 128
 #: the one wide kernel pair: qk head dim up to 192 with v head dim up to 128
 _MAX_WIDE_QK_HEAD_DIM = 192
 _MAX_WIDE_V_HEAD_DIM = 128
+#: the square 256 kernels: qk and v head dim both above the wide qk limit and
+#: at most this
+_MAX_SQUARE_256_HEAD_DIM = 256
 
 
 def head_dim_route(d_qk: int, d_v: int) -> str:
@@ -84,15 +89,22 @@ def head_dim_route(d_qk: int, d_v: int) -> str:
 
     "legacy pad": both dims fit the D = D kernels; the narrower side is
     zero-padded to the wider one. "wide": q, k, v go to the kernel as they
-    are and it runs the <192, 128> pair. Anything else raises ValueError.
+    are and it runs the <192, 128> pair. "square 256": both dims are above
+    192 and at most 256; q, k, v go to the kernel as they are and it runs the
+    <256, 256> kernels. Anything else raises ValueError: a side above 256, or
+    one side at most 192 with the other outside the wide pair.
     """
     if max(d_qk, d_v) <= _MAX_SQUARE_HEAD_DIM:
         return "legacy pad"
     if d_qk <= _MAX_WIDE_QK_HEAD_DIM and d_v <= _MAX_WIDE_V_HEAD_DIM:
         return "wide"
+    if _MAX_WIDE_QK_HEAD_DIM < min(d_qk, d_v) and max(d_qk, d_v) <= _MAX_SQUARE_256_HEAD_DIM:
+        return "square 256"
     raise ValueError(
         f"flash attention supports qk head_dim <= {_MAX_WIDE_QK_HEAD_DIM} with "
-        f"v head_dim <= {_MAX_WIDE_V_HEAD_DIM}; got qk {d_qk}, v {d_v}"
+        f"v head_dim <= {_MAX_WIDE_V_HEAD_DIM}, or qk and v head_dim both in "
+        f"{_MAX_WIDE_QK_HEAD_DIM + 1}..{_MAX_SQUARE_256_HEAD_DIM}; "
+        f"got qk {d_qk}, v {d_v}"
     )
 
 
@@ -101,7 +113,7 @@ def _pad_narrow_side(q, k, v, route: str):
     columns add nothing to PV, zero q/k columns nothing to the dots. F.pad
     keeps it differentiable; the caller slices out[..., :Dv]."""
     Dq, Dv = q.shape[-1], v.shape[-1]
-    if route == "wide" or Dq == Dv:
+    if route != "legacy pad" or Dq == Dv:
         return q, k, v
     import torch.nn.functional as F
 
@@ -114,7 +126,7 @@ class _FlashAttnFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, sinks, causal, softmax_scale, window_left, q_offset):
         ext = get_ext()
-        # the <192, 128> kernels return a third tensor, out's bf16 rounding
+        # the <192, 128> and <256, 256> kernels return a third tensor, out's bf16 rounding
         # residual: the backward's delta = rowsum(dout * out) needs it where
         # the softmax is near one-hot
         out, lse, *out_lo = ext.flash_attn_fwd(
@@ -180,8 +192,8 @@ def flash_attn_func(
     q_offset: int = 0,
 ):
     """Scaled-dot-product attention. q (B,S,Hq,Dqk); k (B,S,Hkv,Dqk);
-    v (B,S,Hkv,Dv); out (B,S,Hq,Dv). On the GPU Dqk and Dv up to 128 each, or
-    Dqk up to 192 with Dv up to 128 (see head_dim_route)."""
+    v (B,S,Hkv,Dv); out (B,S,Hq,Dv). On the GPU Dqk and Dv up to 128 each,
+    Dqk up to 192 with Dv up to 128, or both in 193..256 (see head_dim_route)."""
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(q.shape[-1])
     right_ok = window_size[1] < 0 or causal  # right window only via causality
