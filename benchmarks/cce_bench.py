@@ -20,3 +20,22 @@ def bench(fn, name, flops):
 
 fl = 2.0 * T * V * K
 bench(lambda: _kernel_forward(e, c, tg, 0), "cce fwd kernel", fl)
+
+# forward + backward through the public op, per backward route (D9D_CCE_BWD)
+import os
+from d9d_amd.ops.cce import linear_cross_entropy
+
+e_g = e.clone().requires_grad_(True)
+c_g = c.clone().requires_grad_(True)
+
+
+def fwd_bwd():
+    e_g.grad = c_g.grad = None
+    linear_cross_entropy(e_g, c_g, tg, reduction="mean").backward()
+
+
+for route in ("dense", "sparse", "auto"):
+    os.environ["D9D_CCE_BWD"] = route
+    fwd_bwd()  # auto: the first call is dense and leaves the density behind
+    # TF/s against the dense work (4 GEMMs), whatever the route skips
+    bench(fwd_bwd, f"cce fwd+bwd, {route} backward", 4 * fl)

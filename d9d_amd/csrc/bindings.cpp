@@ -113,6 +113,13 @@ std::vector<torch::Tensor> rope_qk(torch::Tensor q, torch::Tensor k,
 
 // cce.hip
 std::vector<torch::Tensor> cce_fwd(torch::Tensor e, torch::Tensor c, torch::Tensor targets);
+torch::Tensor cce_dlogits_mask_(torch::Tensor logits, torch::Tensor lse, torch::Tensor targets,
+                                torch::Tensor dl, c10::optional<torch::Tensor> dlse,
+                                torch::Tensor mask, int64_t vocab_start, int64_t ignore_index,
+                                double filter_eps, bool write_zeros);
+void cce_bwd_de(torch::Tensor d, torch::Tensor c, torch::Tensor mask, torch::Tensor de);
+void cce_bwd_dc(torch::Tensor d, torch::Tensor e, torch::Tensor mask, torch::Tensor dc,
+                bool accumulate);
 
 // moe_permute.hip
 torch::Tensor moe_gather_rows(torch::Tensor src, torch::Tensor idx, c10::optional<torch::Tensor> scale);
@@ -151,6 +158,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gmm_db", &gmm_db, "CDNA4 grouped GEMM weight-grad");
   m.def("rope_qk", &rope_qk, "fused q/k rotary embedding");
   m.def("cce_fwd", &cce_fwd, "fused linear cross-entropy forward (lse, target logit, lse of the bf16-rounded logits)");
+  m.def("cce_dlogits_mask_", &cce_dlogits_mask_,
+        "fused CCE dlogits (in-place) + 64x128 nonzero-tile mask; write_zeros=false leaves all-zero tiles unwritten");
+  m.def("cce_bwd_de", &cce_bwd_de, "CCE backward de = d @ c over the set tiles");
+  m.def("cce_bwd_dc", &cce_bwd_dc,
+        "CCE backward dc = d^T @ e over the set tiles (bf16 out, or bf16-rounded into an fp32 accumulator)");
   m.def("moe_gather_rows", &moe_gather_rows, "MoE row gather (optional scale)");
   m.def("moe_csr_combine", &moe_csr_combine, "MoE weighted replica combine");
   m.def("moe_row_dot", &moe_row_dot, "per-row dot for prob grads");

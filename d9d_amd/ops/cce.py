@@ -95,6 +95,93 @@ def _can_use_kernel(e, c):
     )
 
 
+# ---- backward route -----------------------------------------------------------
+# With the gradient filter on, most 64 x 128 tiles of a chunk's dlogits are
+# exact zeros, and the sparse route (cce_dlogits_mask_ without the zero
+# writes + cce_bwd_de + cce_bwd_dc, csrc/cce.hip) skips them. Its kernels are
+# simple and only win at low density, so dense chunks keep the library GEMMs.
+_MASK_ROWS, _MASK_COLS = 64, 128
+# Share of set tiles up to which the sparse route is taken: the highest
+# measured density at which it still beat the GEMMs, less one sweep point
+# (profiles/cce_bwd_sparse.md).
+_SPARSE_MAX_DENSITY = 0.15
+
+
+class _BwdRouter:
+    """Chooses dense or sparse from the tile density of an EARLIER backward.
+
+    Reading this backward's density would be a device-to-host sync in the
+    middle of it. Instead every masked backward copies its count of set tiles
+    into a pinned host scalar and records an event; a later call reads the
+    scalar once the event has completed, and until then keeps the last
+    decision. The first call is dense.
+    """
+
+    def __init__(self, threshold=None, new_event=None):
+        self.threshold = _SPARSE_MAX_DENSITY if threshold is None else threshold
+        self.route = "dense"
+        self.density = None  # last density read back
+        self._new_event = new_event or (lambda: torch.cuda.Event())
+        self._host = None
+        self._pending = None  # (event, tiles in the masks counted)
+
+    def poll(self):
+        if self._pending is None:
+            return
+        event, n_tiles = self._pending
+        if not event.query():
+            return
+        self._pending = None
+        self.density = int(self._host) / max(n_tiles, 1)
+        self.route = "sparse" if self.density <= self.threshold else "dense"
+
+    def decide(self):
+        forced = os.environ.get("D9D_CCE_BWD", "auto")
+        if forced in ("dense", "sparse"):
+            return forced
+        if forced != "auto":
+            raise ValueError(f"D9D_CCE_BWD must be auto, dense or sparse, got {forced!r}")
+        if not _capturing():
+            self.poll()
+        return self.route
+
+    def record(self, tiles_set, n_tiles):
+        """tiles_set: 0-d integer tensor on the device (None: nothing ran)."""
+        if tiles_set is None or self._pending is not None or _capturing():
+            return  # one count in flight at a time: the host scalar is its buffer
+        if self._host is None:
+            self._host = torch.zeros((), dtype=torch.int64)
+            if tiles_set.is_cuda:
+                self._host = self._host.pin_memory()
+        self._host.copy_(tiles_set, non_blocking=True)
+        event = self._new_event()
+        event.record()
+        self._pending = (event, n_tiles)
+
+
+def _capturing():
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+_router = _BwdRouter()
+
+
+def _bwd_route(bf16_kernel_path, filter_eps, hidden):
+    """"parent": the unmasked chunked-GEMM backward, untouched (no filter, so
+    no zeros to skip; the eager path; a hidden size the tile kernels do not
+    take; D9D_CCE_BWD=dense). "dense": the same GEMMs behind the masked
+    dlogits kernel, which costs the mask and feeds the router. "sparse": the
+    tile-skipping kernels."""
+    if not bf16_kernel_path or not filter_eps or filter_eps <= 0:
+        return "parent"
+    if hidden % 64 != 0 or hidden > 1024:
+        return "parent"
+    route = _router.decide()
+    if route == "dense" and os.environ.get("D9D_CCE_BWD", "auto") == "dense":
+        return "parent"
+    return route
+
+
 class _LinearCrossEntropyFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e, c, targets, vp_group, vocab_start, vocab_end, filter_eps, softcap):
@@ -169,6 +256,15 @@ class _LinearCrossEntropyFunction(torch.autograd.Function):
             if bf16_fast and T > 0
             else None
         )
+        route = _bwd_route(bf16_fast and T > 0, ctx.filter_eps, H)
+        if route != "parent":
+            n_vt = -(-V // _MASK_COLS)
+            mask_buf = torch.empty(
+                -(-min(chunk, T) // _MASK_ROWS), n_vt, dtype=torch.uint8, device=e.device
+            )
+            tiles_set, tiles_total = None, 0
+            if route == "sparse":
+                e, c = e.contiguous(), c.contiguous()
         for s in range(0, T, chunk):
             sl = slice(s, min(s + _ROW_CHUNK, T))
             e_chunk = e[sl]
@@ -180,7 +276,30 @@ class _LinearCrossEntropyFunction(torch.autograd.Function):
             local_targets = targets[sl] - vocab_start
             in_shard = (local_targets >= 0) & (local_targets < V) & (~ignored[sl])
             safe = local_targets.clamp(0, V - 1)
-            if bf16_fast:
+            if route != "parent":
+                # the same dlogits, plus the mask of 64 x 128 tiles that hold
+                # a nonzero; the sparse route leaves the other tiles unwritten
+                # and its kernels visit the set tiles only
+                mask = mask_buf[: -(-rows // _MASK_ROWS)]
+                pb = get_ext().cce_dlogits_mask_(
+                    logits, lse[sl].float().contiguous(), targets[sl].contiguous(), dl[sl],
+                    dlse_f[sl].contiguous() if dlse_f is not None else None, mask,
+                    vocab_start, LM_IGNORE_INDEX, ctx.filter_eps, route != "sparse",
+                )
+                n_set = mask.sum()
+                tiles_set = n_set if tiles_set is None else tiles_set + n_set
+                tiles_total += mask.numel()
+                if route == "sparse":
+                    get_ext().cce_bwd_de(pb, c, mask, de[sl])
+                    if single:
+                        dc = torch.empty_like(c)
+                    elif dc is None:
+                        dc = torch.empty(V, H, dtype=torch.float32, device=c.device)
+                    # bf16 dc directly, or the chunk's bf16-rounded part into
+                    # the fp32 accumulator (set by the first chunk)
+                    get_ext().cce_bwd_dc(pb, e_chunk, mask, dc, s > 0)
+                    continue
+            elif bf16_fast:
                 # fused in-place dlogits kernel: p = exp(logit - lse), scaled
                 # by (dl + dlse) with the one-hot target column getting -dl;
                 # fp32 math, one pass over (Tc, V)
@@ -215,6 +334,8 @@ class _LinearCrossEntropyFunction(torch.autograd.Function):
                     # vocab: full de = sum_r pb_r @ c_r (reference
                     # reduce_e_grad, d9d/kernel/cce/cce.py:190-198).
                     dist.all_reduce(de, group=vp_group)
+                if route != "parent":
+                    _router.record(tiles_set, tiles_total)
                 return de, dc, None, None, None, None, None, None
             part = torch.matmul(pb.t(), e_chunk.to(c.dtype))
             if dc is None:
@@ -229,6 +350,8 @@ class _LinearCrossEntropyFunction(torch.autograd.Function):
             else:
                 dc += part.float()
 
+        if route != "parent":
+            _router.record(tiles_set, tiles_total)
         if vp_group is not None:
             dist.all_reduce(de, group=vp_group)
         if dc is None:  # T == 0
