@@ -90,6 +90,18 @@ std::vector<torch::Tensor> gdn_chunk_bwd_leaf_wide_varlen(
     torch::Tensor beta, torch::Tensor decay_log, torch::Tensor r,
     torch::Tensor drhs, torch::Tensor s0, torch::Tensor ds0,
     torch::Tensor cu_seqlens);
+// gdn_prep.hip: the block's prologue (q/k L2 norm, GQA expansion, v copy,
+// beta and the decay gate) -> (qn, kn, vt, beta, g), and its backward ->
+// (dq, dk, dv, db_raw, da_raw, dA_log, ddt_bias)
+std::vector<torch::Tensor> gdn_prep_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor b_raw,
+    torch::Tensor a_raw, c10::optional<torch::Tensor> A_log,
+    c10::optional<torch::Tensor> dt_bias);
+std::vector<torch::Tensor> gdn_prep_bwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor b_raw, torch::Tensor a_raw,
+    c10::optional<torch::Tensor> A_log, c10::optional<torch::Tensor> dt_bias,
+    torch::Tensor dqn, torch::Tensor dkn, torch::Tensor dvt,
+    torch::Tensor dbeta, torch::Tensor dg);
 
 torch::Tensor cce_dlogits_(torch::Tensor logits, torch::Tensor lse, torch::Tensor targets,
                            torch::Tensor dl, c10::optional<torch::Tensor> dlse,
@@ -152,6 +164,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "GDN backward per-chunk leaf gradients at head dim 128");
   m.def("gdn_chunk_bwd_leaf_wide_varlen", &gdn_chunk_bwd_leaf_wide_varlen,
         "GDN backward per-chunk leaf gradients at head dim 128, packed documents");
+  m.def("gdn_prep_fwd", &gdn_prep_fwd,
+        "GDN prologue: q/k L2 norm + GQA expansion, v copy, beta and decay gate");
+  m.def("gdn_prep_bwd", &gdn_prep_bwd, "GDN prologue backward");
   m.def("adamw_stochastic_bf16_multi_", &adamw_stochastic_bf16_multi_, "multi-tensor fused SR-AdamW");
   m.def("gmm", &gmm, "CDNA4 grouped GEMM (MoE experts)");
   m.def("gmm_nt", &gmm_nt, "CDNA4 grouped GEMM, weight (E,N,K)");

@@ -2,6 +2,7 @@ from .gated_deltanet import (
     CausalShortDepthwiseConv1d,
     GatedDeltaNet,
     LogSigmoidDecayGate,
+    MambaDecayGate,
     chunk_gated_delta_rule,
     step_gated_delta_rule,
 )
@@ -10,6 +11,7 @@ __all__ = [
     "CausalShortDepthwiseConv1d",
     "GatedDeltaNet",
     "LogSigmoidDecayGate",
+    "MambaDecayGate",
     "chunk_gated_delta_rule",
     "step_gated_delta_rule",
 ]

@@ -1,7 +1,7 @@
 """Gated DeltaNet linear attention (reference: d9d/module/block/attention/linear/gated_deltanet.py).
 
-QKV projections + causal short depthwise conv, log-sigmoid decay gate,
-beta = sigmoid, GQA head expansion, chunked gated delta rule recurrence,
+QKV projections + causal short depthwise conv, log-sigmoid or Mamba decay
+gate, beta = sigmoid, GQA head expansion, chunked gated delta rule recurrence,
 per-head RMSNorm and silu-mul output gate.
 
 The chunked delta-rule recurrence (replacing fla-core's CUDA/Triton
@@ -12,6 +12,7 @@ chunk, all landing on MFMA via rocBLAS. A per-timestep reference recurrence
 """
 
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -19,6 +20,13 @@ from torch import nn
 
 from .....ops import silu_mul
 from .....ops._ext import get_ext, has_ext
+from .....ops.gdn_prep import (
+    gdn_prepare,
+    mamba_decay,
+    prep_bwd_kernel,
+    prep_fwd_kernel,
+    use_prep_kernels,
+)
 from ...normalization import RMSNorm
 
 
@@ -432,7 +440,7 @@ def _gdn_leaf_grads_torch(Qc, Kc, Vc, dOc, bc, gc, Rs, drhss, S0s, dS1s,
 
 
 def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
-                        cu_seqlens=None):
+                        cu_seqlens=None, grads_fp32=False):
     """Explicit backward of `_chunk_gated_delta_rule_torch` (same WY chunk
     formulation), derived by hand so the backward does NOT rebuild and
     backprop the sequential autograd graph. Only the inter-chunk dState
@@ -459,15 +467,35 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
     chunk straddles a boundary. The scans then start from zero at every
     document's first (forward) / last (reverse) chunk, the batched leaf
     code runs unchanged over all chunks, and the results are scattered
-    back to packed rows — no per-document launches."""
+    back to packed rows — no per-document launches.
+
+    `grads_fp32` returns the five gradients in fp32 as computed, not rounded
+    to their tensors' dtypes (the block's prologue backward sums dq, dk over
+    the head group and projects them before any rounding)."""
     B, H, S, Dk = q.shape
     Dv = v.shape[-1]
     dtype_v = v.dtype
-    q32, k32, v32 = q.float(), k.float(), v.float()
-    b32, g32 = beta.float(), decay_log.float()
-    do32 = dout.float()
-
     varlen = cu_seqlens is not None
+    kernels_on = (
+        _use_gdn_kernels(q) and Dk == Dv and Dk in (64, 128)
+        and os.environ.get("D9D_GDN_BWD_SCAN", "1") != "0"
+    )
+    leaf_on = os.environ.get("D9D_GDN_BWD_LEAF", "1") != "0"
+    # dense whole chunks of contiguous bf16 rows with every stage on a kernel:
+    # the kernels read q, k, v, dout as they are (bf16 -> fp32 -> bf16 returns
+    # the same bits) and nothing below needs the fp32 copies
+    direct = (
+        kernels_on and leaf_on and not varlen and chunk_size == 64
+        and S > 0 and S % 64 == 0 and dout.dtype == torch.bfloat16
+        and all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (q, k, v))
+    )
+    if direct:
+        q32 = k32 = v32 = do32 = None
+    else:
+        q32, k32, v32 = q.float(), k.float(), v.float()
+        do32 = dout.float()
+    b32, g32 = beta.float(), decay_log.float()
+
     if varlen:
         cu = _check_cu_seqlens(cu_seqlens, B, S)
         if S == 0:
@@ -511,26 +539,20 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
     first_set = set() if doc_first is None else set(doc_first.tolist())
     last_set = set() if doc_last is None else set(doc_last.tolist())
 
-    # (B, H, nc, C, D) chunked views
-    Qc = q32.view(B, H, nc, C, Dk)
-    Kc = k32.view(B, H, nc, C, Dk)
-    Vc = v32.view(B, H, nc, C, Dv)
-    dOc = do32.view(B, H, nc, C, Dv)
+    # (B, H, nc, C, D) chunked views, for the torch stages
+    if not direct:
+        Qc = q32.view(B, H, nc, C, Dk)
+        Kc = k32.view(B, H, nc, C, Dk)
+        Vc = v32.view(B, H, nc, C, Dv)
+        dOc = do32.view(B, H, nc, C, Dv)
     bc = b32.view(B, H, nc, C)
 
     # ---- the two sequential scans and the per-chunk leaf gradients: CDNA4
     # kernels when they apply, else torch (profiles/gdn_kernels.md)
-    import os
-
-    use_scan_kernels = (
-        _use_gdn_kernels(q) and Dk == Dv and Dk in (64, 128) and C == 64
-        and pad == 0 and os.environ.get("D9D_GDN_BWD_SCAN", "1") != "0"
-    )
+    use_scan_kernels = kernels_on and C == 64 and pad == 0
     # one leaf kernel per head dim; with the flag at 0 the torch stage takes
     # the scan kernels' r, s0, drhs, ds0
-    use_leaf_kernel = (
-        use_scan_kernels and os.environ.get("D9D_GDN_BWD_LEAF", "1") != "0"
-    )
+    use_leaf_kernel = use_scan_kernels and leaf_on
     # the kernels recompute the decay scan and the 64x64 chunk matrices
     # themselves: gc and the prologue exist only for the torch stages
     gc = pro = None
@@ -538,10 +560,13 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
         gc = g32.view(B, H, nc, C).cumsum(dim=-1)
     if use_scan_kernels:
         ext = get_ext()
-        q16 = q32.to(torch.bfloat16).contiguous()
-        k16 = k32.to(torch.bfloat16).contiguous()
-        v16 = v32.to(torch.bfloat16).contiguous()
-        do16 = do32.to(torch.bfloat16).contiguous()
+        if direct:
+            q16, k16, v16, do16 = q, k, v, dout.contiguous()
+        else:
+            q16 = q32.to(torch.bfloat16).contiguous()
+            k16 = k32.to(torch.bfloat16).contiguous()
+            v16 = v32.to(torch.bfloat16).contiguous()
+            do16 = do32.to(torch.bfloat16).contiguous()
         if varlen:
             # boundaries of the document-aligned layout: whole chunks only
             cu_lay = (chunk_off * C).to(torch.int32)
@@ -648,6 +673,8 @@ def _chunk_gdn_backward(q, k, v, beta, decay_log, dout, chunk_size=64,
         return t.index_select(2, row) if varlen else t[:, :, :S]
 
     dq, dk, dv, dbeta, dg = (to_rows(t) for t in (dQ, dK, dV, db, dg))
+    if grads_fp32:
+        return dq, dk, dv, dbeta, dg
     return (
         dq.to(q.dtype), dk.to(k.dtype), dv.to(dtype_v),
         dbeta.to(beta.dtype), dg.to(decay_log.dtype),
@@ -671,6 +698,71 @@ class LogSigmoidDecayGate(nn.Module):
         return F.logsigmoid(self.proj(x).float())
 
 
+class MambaDecayGate(nn.Module):
+    """a_t = -exp(A_log) * softplus(w x + dt_bias) -> log decay in (-inf, 0),
+    per-head A_log and dt_bias kept in fp32 (the gate Qwen3-Next uses)."""
+
+    def __init__(
+        self,
+        hidden_size: int,
+        num_heads: int,
+        normalizer: float = 16.0,
+        dt_min: float = 1e-3,
+        dt_max: float = 0.1,
+        dt_init_floor: float = 1e-4,
+        device=None,
+        dtype=None,
+    ):
+        super().__init__()
+        self.proj = nn.Linear(hidden_size, num_heads, bias=False, device=device, dtype=dtype)
+        self.A_log = nn.Parameter(torch.empty(num_heads, device=device, dtype=torch.float32))
+        self.dt_bias = nn.Parameter(torch.empty(num_heads, device=device, dtype=torch.float32))
+        self.normalizer = normalizer
+        self.dt_min, self.dt_max, self.dt_init_floor = dt_min, dt_max, dt_init_floor
+
+    def reset_parameters(self) -> None:
+        with torch.no_grad():
+            nn.init.normal_(self.proj.weight, std=0.02)
+            # A ~ U(0, normalizer); dt log-uniform in [dt_min, dt_max], floored,
+            # and dt_bias its inverse softplus, so softplus(dt_bias) = dt
+            self.A_log.copy_(torch.log(torch.empty_like(self.A_log).uniform_(0.0, self.normalizer)))
+            log_dt = torch.empty_like(self.dt_bias).uniform_(
+                math.log(self.dt_min), math.log(self.dt_max))
+            dt = torch.exp(log_dt).clamp(min=self.dt_init_floor)
+            self.dt_bias.copy_(dt + torch.log(-torch.expm1(-dt)))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:  # (B,S,H) log decay
+        return mamba_decay(self.proj(x), self.A_log, self.dt_bias)
+
+
+class _GdnPrepChunkFunction(torch.autograd.Function):
+    """The HIP prologue (csrc/gdn_prep.hip) and the chunked recurrence as one
+    autograd node. Autograd rounds a gradient to its tensor's dtype, so with
+    two nodes the gradients of the bf16 qn, kn would be rounded to bf16
+    before the prologue's backward sums them over the head group and
+    projects them -- a projection that cancels. Here `_chunk_gdn_backward`
+    hands its fp32 results straight to `gdn_prep_bwd`."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, b_raw, a_raw, A_log, dt_bias, cu_seqlens):
+        qn, kn, vt, beta, g = prep_fwd_kernel(q, k, v, b_raw, a_raw, A_log, dt_bias)
+        if has_ext() and qn.shape[-1] == vt.shape[-1]:
+            out = _gdn_kernel_fwd(qn, kn, vt, beta, g, cu_seqlens)
+        else:
+            out = _chunk_gated_delta_rule_torch(qn, kn, vt, beta, g, 64, cu_seqlens)
+        ctx.save_for_backward(q, k, b_raw, a_raw, A_log, dt_bias, qn, kn, vt, beta, g)
+        ctx.cu_seqlens = cu_seqlens
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        *inputs, qn, kn, vt, beta, g = ctx.saved_tensors
+        grads = _chunk_gdn_backward(
+            qn, kn, vt, beta, g, dout, 64, ctx.cu_seqlens, grads_fp32=True
+        )
+        return (*prep_bwd_kernel(*inputs, *grads), None)
+
+
 class GatedDeltaNet(nn.Module):
     """Gated delta-rule linear attention with short convs and an output gate.
     On the GPU the recurrence runs on the HIP chunk kernels when
@@ -685,10 +777,13 @@ class GatedDeltaNet(nn.Module):
         head_v_dim: int = 64,
         conv_kernel_size: int = 4,
         rms_norm_eps: float = 1e-6,
+        decay_gate: str = "logsigmoid",
         device=None,
         dtype=None,
     ) -> None:
         super().__init__()
+        if decay_gate not in ("logsigmoid", "mamba"):
+            raise ValueError(f"decay_gate must be 'logsigmoid' or 'mamba', got {decay_gate!r}")
         kw = {"device": device, "dtype": dtype, "bias": False}
         self.num_heads = num_heads
         self.num_kv_heads = num_kv_heads or num_heads
@@ -706,7 +801,8 @@ class GatedDeltaNet(nn.Module):
             num_heads * head_v_dim, conv_kernel_size, device=device, dtype=dtype)
 
         self.beta_proj = nn.Linear(hidden_size, num_heads, **kw)
-        self.decay_gate = LogSigmoidDecayGate(hidden_size, num_heads, device=device, dtype=dtype)
+        gate_cls = MambaDecayGate if decay_gate == "mamba" else LogSigmoidDecayGate
+        self.decay_gate = gate_cls(hidden_size, num_heads, device=device, dtype=dtype)
 
         self.out_norm = RMSNorm(head_v_dim, eps=rms_norm_eps, device=device, dtype=dtype)
         self.out_gate = nn.Linear(hidden_size, num_heads * head_v_dim, **kw)
@@ -743,26 +839,30 @@ class GatedDeltaNet(nn.Module):
         v = self.v_conv(self.v_proj(hidden_states), cu_seqlens).view(
             B, S, H, self.head_v_dim)
 
-        if H != Hkv:  # GQA expansion
-            rep = H // Hkv
-            q = q.repeat_interleave(rep, dim=2)
-            k = k.repeat_interleave(rep, dim=2)
-
-        # L2-normalize q/k per head (delta-rule convention)
-        q = F.normalize(q.float(), dim=-1)
-        k = F.normalize(k.float(), dim=-1)
-
-        beta = torch.sigmoid(self.beta_proj(hidden_states).float())  # (B,S,H)
-        decay = self.decay_gate(hidden_states)  # (B,S,H)
-
-        out = chunk_gated_delta_rule(
-            q.permute(0, 2, 1, 3),
-            k.permute(0, 2, 1, 3),
-            v.permute(0, 2, 1, 3).to(v.dtype),
-            beta.permute(0, 2, 1),
-            decay.permute(0, 2, 1),
-            cu_seqlens=cu_seqlens,
-        ).permute(0, 2, 1, 3)  # (B,S,H,Dv)
+        # GQA expansion, q/k L2 norm, beta and the log decay, all (B,H,S,..):
+        # one HIP pass on the GPU (ops/gdn_prep.py)
+        b_raw = self.beta_proj(hidden_states)  # (B,S,H)
+        a_raw = self.decay_gate.proj(hidden_states)
+        gate = {}
+        if isinstance(self.decay_gate, MambaDecayGate):
+            gate = {"A_log": self.decay_gate.A_log, "dt_bias": self.decay_gate.dt_bias}
+        leaves = (q, k, v, b_raw, a_raw, *gate.values())
+        if (
+            use_prep_kernels(q, k, v, b_raw, a_raw)
+            and torch.is_grad_enabled()
+            and any(t.requires_grad for t in leaves)
+        ):
+            if cu_seqlens is not None:
+                _check_cu_seqlens(cu_seqlens, B, S)
+            out = _GdnPrepChunkFunction.apply(
+                q, k, v, b_raw, a_raw, gate.get("A_log"), gate.get("dt_bias"),
+                cu_seqlens,
+            )
+        else:
+            out = chunk_gated_delta_rule(
+                *gdn_prepare(q, k, v, b_raw, a_raw, **gate), cu_seqlens=cu_seqlens
+            )
+        out = out.permute(0, 2, 1, 3)  # (B,S,H,Dv)
 
         out = self.out_norm(out)
         gate = self.out_gate(hidden_states).view(B, S, H, self.head_v_dim)

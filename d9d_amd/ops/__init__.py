@@ -3,6 +3,7 @@ from .swiglu import silu_mul, silu_mul_packed
 from .stochastic import copy_fp32_to_bf16_stochastic_, adamw_stochastic_bf16_
 from .attention import flash_attn_func, flash_attn_varlen_func
 from .cce import linear_cross_entropy, LM_IGNORE_INDEX, VocabParallelOptions
+from .gdn_prep import gdn_prepare
 from .gmm import gmm, gmm_nt
 from .moe_permute import moe_permute, moe_unpermute
 from .router import router_topk
@@ -19,6 +20,7 @@ __all__ = [
     "linear_cross_entropy",
     "LM_IGNORE_INDEX",
     "VocabParallelOptions",
+    "gdn_prepare",
     "gmm",
     "gmm_nt",
     "moe_permute",

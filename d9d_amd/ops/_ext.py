@@ -31,6 +31,7 @@ _SOURCES = [
     "attention.hip",
     "cce.hip",
     "gdn.hip",
+    "gdn_prep.hip",
 ]
 
 _ext_module = None

@@ -574,6 +574,12 @@ def parallelize_tp_gdn(
     projections and the causal-conv channels shard with the heads, o_proj
     rowwise; the per-head-dim output RMSNorm weight is shared across heads
     (replicated inside the region, tp-sum grads)."""
+    from ..module.block.attention.linear import MambaDecayGate
+
+    if isinstance(gdn.decay_gate, MambaDecayGate):
+        raise NotImplementedError(
+            "parallelize_tp_gdn does not shard the Mamba decay gate's A_log and dt_bias yet"
+        )
     tp_dim = mesh.mesh_dim_names.index(tp_dim_name)
     tp_size = mesh.shape[tp_dim]
     if tp_size == 1:
