@@ -124,7 +124,8 @@ std::vector<torch::Tensor> rope_qk(torch::Tensor q, torch::Tensor k,
                                    torch::Tensor cos_t, torch::Tensor sin_t, double sin_sign);
 
 // cce.hip
-std::vector<torch::Tensor> cce_fwd(torch::Tensor e, torch::Tensor c, torch::Tensor targets);
+std::vector<torch::Tensor> cce_fwd(torch::Tensor e, torch::Tensor c, torch::Tensor targets,
+                                   int64_t n_spans);
 torch::Tensor cce_dlogits_mask_(torch::Tensor logits, torch::Tensor lse, torch::Tensor targets,
                                 torch::Tensor dl, c10::optional<torch::Tensor> dlse,
                                 torch::Tensor mask, int64_t vocab_start, int64_t ignore_index,
@@ -172,7 +173,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gmm_nt", &gmm_nt, "CDNA4 grouped GEMM, weight (E,N,K)");
   m.def("gmm_db", &gmm_db, "CDNA4 grouped GEMM weight-grad");
   m.def("rope_qk", &rope_qk, "fused q/k rotary embedding");
-  m.def("cce_fwd", &cce_fwd, "fused linear cross-entropy forward (lse, target logit, lse of the bf16-rounded logits)");
+  m.def("cce_fwd", &cce_fwd,
+        "fused linear cross-entropy forward (lse, target logit, lse of the bf16-rounded logits); "
+        "n_spans: vocab spans per row tile, 0 = choose",
+        py::arg("e"), py::arg("c"), py::arg("targets"), py::arg("n_spans") = 0);
   m.def("cce_dlogits_mask_", &cce_dlogits_mask_,
         "fused CCE dlogits (in-place) + 64x128 nonzero-tile mask; write_zeros=false leaves all-zero tiles unwritten");
   m.def("cce_bwd_de", &cce_bwd_de, "CCE backward de = d @ c over the set tiles");

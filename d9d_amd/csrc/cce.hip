@@ -6,15 +6,21 @@
 // logit, WITHOUT materializing the (T, V) logits. The (T,V) GEMM runs on
 // MFMA inside the kernel with an online logsumexp.
 //
-// Geometry: one block = 64 token rows (4 waves x 16-row m-tile). The token
-// block's embeddings (64 x K bf16) live in LDS for the whole sweep; the
-// classifier streams as (64 vocab x 64 k) tiles, T14-staged (loads issued a
-// tile early into registers, written to the alternate LDS buffer after the
-// MFMAs). All resident blocks sweep the vocab in the same order, so the
-// classifier is served from L2/L3 after the first wavefront of blocks.
+// FORWARD. The GEMM is e (T, K) against c (V, K), both k-contiguous: the
+// grouped GEMM's (E, N, K) case with one expert, and cce_fwd_tiled_kernel
+// runs it on that kernel's loop (gmm_8phase_kernel<256, false>, gmm.hip):
+// 256 token rows x 256 vocab columns per tile, 64-wide k-tiles staged by
+// global_load_lds into two 64 KB LDS slots behind counted vmcnt waits, 8 waves
+// as 2 x 4 with a 128 x 64 accumulator each. A block keeps one row tile and
+// walks a contiguous span of vocab tiles; the k-tile pipeline runs straight
+// through the vocab-tile boundaries. When a tile's logits are complete each
+// wave folds its 128 x 64 of them into a running (m, l, lb) per row, kept in
+// LDS per column quarter, and picks up the target logit by column compare.
+// Each block writes its rows' partial (m, l, lb, tgt) to a workspace and
+// cce_fwd_merge_kernel combines the spans of a row in span order: no atomics,
+// the same bits on every launch.
 //
-// K (hidden) is a runtime dim; K <= 1024 fits the 160 KiB LDS (the host
-// falls back to the chunked rocBLAS path above that).
+// K (hidden) is a runtime dim, a multiple of 64.
 //
 // BACKWARD (second half of this file). The logits of a row chunk are
 // recomputed by the library GEMM and turned into dlogits in place. With the
@@ -26,6 +32,7 @@
 // from the tile density of the previous backward.
 #include "common.h"
 #include "mfma.h"
+#include "glds_tile.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -34,270 +41,408 @@ namespace d9d {
 
 constexpr float kLog2eC = 1.44269504088896340736f;
 
-// KT = k-tile width (128 when K % 128 == 0): wider k-tiles double the MFMA
-// work between barriers (16 vs 8 per wave); the classifier tile is
-// single-buffered with T14 register staging (the registers are the second
-// buffer), like the grouped-GEMM kernels.
-template <int KT>
-__global__ __launch_bounds__(512, 2) void cce_fwd_kernel(
-    const bf16_t* __restrict__ e,   // (T, K)
-    const bf16_t* __restrict__ c,   // (V, K)
-    const int64_t* __restrict__ targets,  // (T,)
-    float* __restrict__ lse_out,          // (T,)
-    float* __restrict__ tgt_out,          // (T,) target logit or -inf
-    float* __restrict__ lse_bf_out,       // (T,) lse of the bf16-ROUNDED logits
-    int T, int V, int K) {
+constexpr int kFwdTile = 256;                // token rows = vocab columns per tile
+constexpr int kFwdSlot = (256 + 256) * 128;  // one k-tile: A 32 KB + B 32 KB
+// Row tiles that run side by side on one XCD. Work ids go row tile fastest
+// inside a group of this many, then span, then group (see the kernel), and
+// xcd_remap hands an XCD consecutive ids: its 32 CUs hold 8 row tiles x 4
+// spans, so 8 e tiles (3 MB at K = 768) stay in its 4 MB L2 and each
+// classifier k-tile it fetches serves 8 blocks.
+constexpr int kFwdRowGroup = 8;
+// LDS behind the two slots: (m, l, lb) per column quarter and row, the target
+// logit and the target column per row.
+constexpr int kFwdStateFloats = 3 * 4 * kFwdTile + 2 * kFwdTile;
+constexpr int kFwdLds = 2 * kFwdSlot + kFwdStateFloats * 4;
+
+// A lane's value as seen from another lane of its 16-lane DPP row.
+template <int CTRL>
+D9D_DEVICE float dpp_row(float v) {
+  const int x = __builtin_bit_cast(int, v);
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true));
+}
+// Reductions over the 16 lanes that share lane >> 4 (the 16 columns of one
+// accumulator subtile): quad_perm [1,0,3,2], quad_perm [2,3,0,1],
+// row_half_mirror, row_mirror. After the two quad steps a quad is uniform,
+// so the mirrors bring in the other quad and then the other half. The order
+// is fixed, and every lane ends with the same bits.
+D9D_DEVICE float row16_max(float v) {
+  v = fmaxf(v, dpp_row<0xB1>(v));
+  v = fmaxf(v, dpp_row<0x4E>(v));
+  v = fmaxf(v, dpp_row<0x141>(v));
+  return fmaxf(v, dpp_row<0x140>(v));
+}
+D9D_DEVICE float row16_sum(float v) {
+  v += dpp_row<0xB1>(v);
+  v += dpp_row<0x4E>(v);
+  v += dpp_row<0x141>(v);
+  return v + dpp_row<0x140>(v);
+}
+
+// gmm_8phase_kernel's stage_a (gmm.hip) as a function. One thread's two glds
+// of a 128-row half (16 KB) of a 256-row, k-contiguous A tile: rows
+// row0 + half * 128 .. of the (rows, K) matrix `a` at k offset k0, into a_slot + half * 16 KB. The tile is [256][kBK] row-major with the
+// row-keyed swizzle, produced by PRE-SWIZZLING the per-lane global source
+// address (glds writes linearly: wave-uniform base + lane*16). Rows at or past
+// row_end are clamped to row_end - 1.
+D9D_DEVICE void stage_a_half(const bf16_t* __restrict__ a, char* a_slot,
+                             int k0, int row0, int row_end, int K, int half,
+                             int wave, int lane) {
+  char* base = a_slot + half * (16 * 1024);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int chunk = wave + i * 8;           // 16 chunks of 1 KB
+    const int l = chunk * 1024 + lane * 16;   // linear LDS byte in half
+    const int arow = half * 128 + (l >> 7);   // tile row (128-B rows)
+    const int colb = (l & 127) ^ ((arow & 7) << 4);  // source pre-swizzle
+    const int64_t sr = min(row0 + arow, row_end - 1);
+    glds16(reinterpret_cast<const char*>(a) + (sr * (int64_t)K + k0) * 2 + colb,
+           base + l);
+  }
+}
+
+// Forward main kernel: partial (m, l, lb, tgt) of one 256-row tile over one
+// span of vocab tiles. The loop is gmm_8phase_kernel<256, false>'s (gmm.hip)
+// with the linear iteration `it` over (vocab tile, k-tile) in place of kt:
+// same slots (parity of it), same staging order, same counted waits, same raw
+// barriers; see the schedule written out above that kernel. A(it) is the e
+// k-tile it % n_ktiles, B(it) the classifier k-tile of its vocab tile, so the
+// staging of the next vocab tile is in flight while a tile's epilogue runs.
+// Every logit accumulates its 32-wide k-steps in ascending order in one chain.
+__global__ __launch_bounds__(512, 1) void cce_fwd_tiled_kernel(
+    const bf16_t* __restrict__ e,         // (T, K)
+    const bf16_t* __restrict__ c,         // (V, K)
+    const int64_t* __restrict__ targets,  // (T,) local column, or outside [0, V)
+    float* __restrict__ ws,               // (4, n_spans, T): m, l, lb, tgt
+    int T, int V, int K, int n_rt, int n_spans) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* e_lds = reinterpret_cast<bf16_t*>(smem);       // [64][K] swizzled
-  bf16_t* c_lds = e_lds + 64 * K;                        // [128][KT] swizzled
-  // XOR swizzles must stay inside their LDS row. The classifier tile has
-  // KT*2-byte rows. The e rows are K*2 bytes: a multiple of 256 when
-  // K % 128 == 0 (always the case at KT == 128), but only of 128 otherwise,
-  // where a 4-bit XOR would spill into the next row (and, from row 63, into
-  // the classifier tile). So e_lds and c_lds both swizzle with kSwz: 3 bits
-  // at KT == 64, 4 bits at KT == 128.
-  constexpr int kSwz = (KT == 64) ? 7 : 15;
+  float* st_m = reinterpret_cast<float*>(smem + 2 * kFwdSlot);  // [4][256]
+  float* st_l = st_m + 4 * kFwdTile;                            // [4][256]
+  float* st_lb = st_l + 4 * kFwdTile;                           // [4][256]
+  float* tgt_lds = st_lb + 4 * kFwdTile;                        // [256]
+  int* tg_lds = reinterpret_cast<int*>(tgt_lds + kFwdTile);     // [256]
 
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;   // 8 waves: (vocab half) x (4 m-tiles)
-  const int m_tile = wave & 3;
-  const int vhalf = wave >> 2;
-  const int t0 = blockIdx.x * 64;
+  const int wave = threadIdx.x >> 6;
+  const int wm = wave >> 2;   // row half: 128 rows
+  const int wn = wave & 3;    // column quarter: 64 columns
 
-  const int n_vtiles = (V + 127) / 128;  // 128-wide vocab tiles (2 x 64 halves)
-  const int n_ktiles = K / KT;
-  const int total_iters = n_vtiles * n_ktiles;
+  // work id -> (row tile, span): row tile fastest within a group of
+  // kFwdRowGroup row tiles (the last group may be smaller), then span.
+  const int wid = xcd_remap(blockIdx.x, gridDim.x);
+  const int per_group = kFwdRowGroup * n_spans;
+  const int rg = wid / per_group;
+  const int gs = min(kFwdRowGroup, n_rt - rg * kFwdRowGroup);
+  const int rem = wid - rg * per_group;
+  const int span = rem / gs;
+  const int row0 = (rg * kFwdRowGroup + rem % gs) * kFwdTile;
 
-  constexpr int kCRegs = KT / 32;  // (128 * KT) / (512 threads * 8)
-  bf16x8 c_reg[kCRegs];
-  auto load_c = [&](int it_lin) {
-    const int vt = it_lin / n_ktiles;
-    const int kt = it_lin % n_ktiles;
-#pragma unroll
-    for (int i = 0; i < kCRegs; ++i) {
-      const int idx = (threadIdx.x + i * 512) * 8;
-      const int vrow = idx / KT;
-      const int col = idx % KT;
-      const int g_v = min(vt * 128 + vrow, V - 1);
-      c_reg[i] = *reinterpret_cast<const bf16x8*>(
-          c + (int64_t)g_v * K + kt * KT + col);
-    }
-  };
-  auto store_c = [&]() {
-#pragma unroll
-    for (int i = 0; i < kCRegs; ++i) {
-      const int idx = (threadIdx.x + i * 512) * 8;
-      const int vrow = idx / KT;
-      const int col = idx % KT;
-      const int byte = (col * 2) ^ ((vrow & kSwz) << 4);
-      *reinterpret_cast<bf16x8*>(
-          reinterpret_cast<char*>(c_lds) + vrow * (KT * 2) + byte) = c_reg[i];
-    }
-  };
+  const int n_vt = (V + kFwdTile - 1) / kFwdTile;
+  const int vt_lo = (int)((int64_t)span * n_vt / n_spans);
+  const int vt_hi = (int)((int64_t)(span + 1) * n_vt / n_spans);
+  const int n_ktiles = K / kBK;
+  const int n_it = (vt_hi - vt_lo) * n_ktiles;
 
-  // ---- stage e block (row-major [64][K], ((row&kSwz)<<4) swizzle) and the
-  // first classifier tile; ONE barrier covers both ---------------------------
-  for (int idx = threadIdx.x * 8; idx < 64 * K; idx += 512 * 8) {
-    const int row = idx / K;
-    const int col = idx % K;
-    const int g_row = min(t0 + row, T - 1);
-    const bf16x8 val = *reinterpret_cast<const bf16x8*>(e + (int64_t)g_row * K + col);
-    const int byte = (col * 2) ^ ((row & kSwz) << 4);
-    *reinterpret_cast<bf16x8*>(
-        reinterpret_cast<char*>(e_lds) + row * (K * 2) + byte) = val;
-  }
-  load_c(0);
-  store_c();
-  __syncthreads();
-
-  const int my_row_local = m_tile * 16 + (lane & 15);
-
-  // lb_run: what the online sum gains when every logit z is rounded to bf16
+  // lb: what the online sum gains when every logit z is rounded to bf16
   // (zb), to first order: sum exp(z - m) * (zb - z); exp(zb - z) - 1 - (zb - z)
   // is below (2^-9 z)^2 / 2: 5e-4 at |z| < 16 and 2e-3 at |z| < 32 (under the
   // 4e-3 bf16 step of the dlogits), 8e-3 at |z| < 64. The form assumes
-  // |z| < 64; at |z| >= 128 the rounding step is 0.5 and it no longer holds. The backward recomputes the logits as a bf16
-  // GEMM output, and exp(bf16 logit - lse) only sums to 1 over a row against
+  // |z| < 64; at |z| >= 128 the rounding step is 0.5 and it no longer holds.
+  // The backward recomputes the logits as a bf16 GEMM output, and
+  // exp(bf16 logit - lse) only sums to 1 over a row against
   // the lse of the ROUNDED logits: against the fp32 one every p is off by the
   // rounding of its own logit (up to 3% at |logit| in [8, 16)).
-  float m_run[4], l_run[4], lb_run[4], tgt[4];
-  int tg_row[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    m_run[r] = -1e30f;
-    l_run[r] = 0.f;
-    lb_run[r] = 0.f;
-    tgt[r] = -1e30f;
-    tg_row[r] = (int)targets[min(t0 + m_tile * 16 + (lane >> 4) * 4 + r, T - 1)];
+  for (int i = threadIdx.x; i < 4 * kFwdTile; i += 512) {
+    st_m[i] = -1e30f;
+    st_l[i] = 0.f;
+    st_lb[i] = 0.f;
   }
+  if (threadIdx.x < kFwdTile) {
+    tgt_lds[threadIdx.x] = -1e30f;
+    tg_lds[threadIdx.x] = (int)targets[min(row0 + (int)threadIdx.x, T - 1)];
+  }
+  __syncthreads();  // before the first glds: the counted waits start clean
+  // two of this wave's 128 rows per lane, for the per-tile target test
+  const int tg_a = tg_lds[wm * 128 + lane];
+  const int tg_b = tg_lds[wm * 128 + 64 + lane];
 
-  f32x4 acc[4];
+  f32x4 acc[8][4];
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  for (int it = 0; it < total_iters; ++it) {
-    const int vt = it / n_ktiles;
-    const int kt = it % n_ktiles;
-    if (it + 1 < total_iters) load_c(it + 1);  // issue early, store late
+  auto stage_a = [&](int it_x, int kt_x, int half) {
+    stage_a_half(e, smem + (size_t)(it_x & 1) * kFwdSlot, kt_x * kBK, row0, T,
+                 K, half, wave, lane);
+  };
+  auto stage_b = [&](int it_x, int vt_x, int kt_x, int chunk) {
+    Tile8BNK<256>::stage(c, smem + (size_t)(it_x & 1) * kFwdSlot + 32 * 1024,
+                         kt_x * kBK, vt_x * kFwdTile, K, V, chunk, wave, lane);
+  };
+  auto advance = [&](int& vt_x, int& kt_x) {
+    if (++kt_x == n_ktiles) { kt_x = 0; ++vt_x; }
+  };
 
-    __builtin_amdgcn_s_setprio(1);
+  // Logits of vocab tile vt are complete in acc: fold this wave's 128 rows x
+  // 64 columns into the rows' running state of column quarter wn. Only this
+  // wave touches that state, so the epilogue needs no barrier.
+  auto epilogue = [&](int vt) {
+    const int col_lo = vt * kFwdTile + wn * 64;
+    const int lcol = col_lo + (lane & 15);  // column of subtile j: lcol + 16 j
+    if (col_lo + 64 > V) {  // padded columns (the last tile only)
 #pragma unroll
-    for (int ks = 0; ks < KT / 32; ++ks) {
-      const int kk = kt * KT + ks * 32 + (lane >> 4) * 8;
-      const int ebyte = (kk * 2) ^ ((my_row_local & kSwz) << 4);
-      const bf16x8 ea = *reinterpret_cast<const bf16x8*>(
-          reinterpret_cast<char*>(e_lds) + my_row_local * (K * 2) + ebyte);
+      for (int j = 0; j < 4; ++j) {
+        if (lcol + j * 16 >= V) {
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const int vrow = vhalf * 64 + nt * 16 + (lane & 15);
-        const int cbyte =
-            ((ks * 32 + (lane >> 4) * 8) * 2) ^ ((vrow & kSwz) << 4);
-        const bf16x8 cb = *reinterpret_cast<const bf16x8*>(
-            reinterpret_cast<const char*>(c_lds) + vrow * (KT * 2) + cbyte);
-        acc[nt] = mfma16(ea, cb, acc[nt]);
+          for (int i = 0; i < 8; ++i) acc[i][j] = {-1e30f, -1e30f, -1e30f, -1e30f};
+        }
       }
     }
-    __builtin_amdgcn_s_setprio(0);
-
-    if (kt == n_ktiles - 1) {
-      // Logits tile complete. PER-LANE online lse over this lane's own 4
-      // columns — the 16-lane merge happens ONCE after the sweep, so the
-      // hot epilogue has NO cross-lane shuffles (they were ~2/3 of the
-      // per-tile VALU work: 96 shfl_xor per vocab tile).
-      float vals[4][4];
+    // Target by column compare, only where one of the wave's rows has its
+    // target among these 64 columns. One (row, column) has one owner in the
+    // whole grid, so a plain store does it. A target at or past V (another
+    // shard's) is left at -1e30.
+    const bool hit = (unsigned)(tg_a - col_lo) < 64u || (unsigned)(tg_b - col_lo) < 64u;
+    // (rbase goes through an empty asm so that the addresses derived from it
+    // are formed here, as base + immediate, and not kept in registers across
+    // the main loop, where they spill.)
+    int rbase = wm * 128 + (lane >> 4) * 4;  // row of subtile i, register r: rbase + 16 i + r
+    asm volatile("" : "+v"(rbase));
+    if (__ballot(hit)) {
+      const int* tg_p = tg_lds + rbase;
+      float* tgt_p = tgt_lds + rbase;
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const int col = vt * 128 + vhalf * 64 + nt * 16 + (lane & 15);
+      for (int i = 0; i < 8; ++i) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          vals[nt][r] = (col < V) ? acc[nt][r] : -1e30f;
+          const int tg = tg_p[i * 16 + r];
+          const int d = tg - lcol;
+          float val = acc[i][0][r];
+#pragma unroll
+          for (int j = 1; j < 4; ++j) val = (d == j * 16) ? acc[i][j][r] : val;
+          if ((d & ~48) == 0 && tg < V) tgt_p[i * 16 + r] = val;
         }
       }
+    }
+    float* st_p = st_m + wn * kFwdTile + rbase;  // l and lb: 4 and 8 * kFwdTile on
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      // one row subtile at a time: scheduled together, the eight subtiles'
+      // state and temporaries do not fit beside the accumulators
+      __builtin_amdgcn_sched_barrier(0);
+      f32x4 m4 = *reinterpret_cast<const f32x4*>(st_p + i * 16);
+      f32x4 l4 = *reinterpret_cast<const f32x4*>(st_p + 4 * kFwdTile + i * 16);
+      f32x4 lb4 = *reinterpret_cast<const f32x4*>(st_p + 8 * kFwdTile + i * 16);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          const int col = vt * 128 + vhalf * 64 + nt * 16 + (lane & 15);
-          if (col == (int)tg_row[r]) tgt[r] = fmaxf(tgt[r], vals[nt][r]);
-        }
-        const float mx = fmaxf(fmaxf(vals[0][r], vals[1][r]),
-                               fmaxf(vals[2][r], vals[3][r]));
-        const float m_new = fmaxf(m_run[r], mx);
+        const float mx = row16_max(fmaxf(fmaxf(acc[i][0][r], acc[i][1][r]),
+                                         fmaxf(acc[i][2][r], acc[i][3][r])));
+        const float m_new = fmaxf(m4[r], mx);
         float add = 0.f, add_bf = 0.f;
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          const float ex =
-              __builtin_amdgcn_exp2f((vals[nt][r] - m_new) * kLog2eC);
+        for (int j = 0; j < 4; ++j) {
+          const float v = acc[i][j][r];
+          const float ex = __builtin_amdgcn_exp2f((v - m_new) * kLog2eC);
           add += ex;
           // native RNE convert on gfx950
-          const float vb = static_cast<float>(static_cast<bf16_t>(vals[nt][r]));
-          add_bf = fmaf(ex, vb - vals[nt][r], add_bf);
+          const float vb = static_cast<float>(static_cast<bf16_t>(v));
+          add_bf = fmaf(ex, vb - v, add_bf);
         }
-        const float rescale =
-            __builtin_amdgcn_exp2f((m_run[r] - m_new) * kLog2eC);
-        l_run[r] = l_run[r] * rescale + add;
-        lb_run[r] = lb_run[r] * rescale + add_bf;
-        m_run[r] = m_new;
+        add = row16_sum(add);
+        add_bf = row16_sum(add_bf);
+        const float rescale = __builtin_amdgcn_exp2f((m4[r] - m_new) * kLog2eC);
+        l4[r] = l4[r] * rescale + add;
+        lb4[r] = lb4[r] * rescale + add_bf;
+        m4[r] = m_new;
+      }
+      if ((lane & 15) == 0) {
+        *reinterpret_cast<f32x4*>(st_p + i * 16) = m4;
+        *reinterpret_cast<f32x4*>(st_p + 4 * kFwdTile + i * 16) = l4;
+        *reinterpret_cast<f32x4*>(st_p + 8 * kFwdTile + i * 16) = lb4;
       }
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) acc[nt] = {0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
     }
+  };
 
-    __syncthreads();
-    if (it + 1 < total_iters) {
-      store_c();
-      __syncthreads();
-    }
+  // (vocab tile, k-tile) of iterations it, it + 1 and it + 2
+  int vt0 = vt_lo, kt0 = 0;
+  int vt1 = vt0, kt1 = kt0;
+  advance(vt1, kt1);
+  int vt2 = vt1, kt2 = kt1;
+  advance(vt2, kt2);
+
+  // Prologue: issue order matches the steady-state boundary count.
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch) stage_b(0, vt0, kt0, ch);
+  stage_a(0, kt0, 0); stage_a(0, kt0, 1);
+  if (n_it > 1) {
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) stage_b(1, vt1, kt1, ch);
   }
 
-  // ---- merge this wave's 16 col-lanes (once per kernel), then the two
-  // vocab halves; write lse + target logit ----------------------------------
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) {
-      const float mo = __shfl_xor(m_run[r], off, 64);
-      const float lo = __shfl_xor(l_run[r], off, 64);
-      const float lbo = __shfl_xor(lb_run[r], off, 64);
-      const float m2 = fmaxf(m_run[r], mo);
-      const float sa = __builtin_amdgcn_exp2f((m_run[r] - m2) * kLog2eC);
-      const float sb = __builtin_amdgcn_exp2f((mo - m2) * kLog2eC);
-      l_run[r] = l_run[r] * sa + lo * sb;
-      lb_run[r] = lb_run[r] * sa + lbo * sb;
-      m_run[r] = m2;
-      tgt[r] = fmaxf(tgt[r], __shfl_xor(tgt[r], off, 64));
+  for (int it = 0; it < n_it; ++it) {
+    const char* a_base = smem + (size_t)(it & 1) * kFwdSlot;
+    const char* b_base = a_base + 32 * 1024;
+
+    // Boundary: this iteration's staging landed. In steady state the 4 newer
+    // loads are B(it + 1); on the last iteration the newest outstanding loads
+    // are this one's A halves, so drain fully.
+    if (it + 1 < n_it) {
+      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-  }
-  // scratch (reuses c_lds): per half, per row: lse, tgt and rounded lse.
-  float* half_lse = reinterpret_cast<float*>(c_lds);          // [2][64]
-  float* half_tgt = half_lse + 2 * 64;                        // [2][64]
-  float* half_lbf = half_tgt + 2 * 64;                        // [2][64]
-  __syncthreads();
-  if ((lane & 15) == 0) {
+    __builtin_amdgcn_s_barrier();
+
+    bf16x8 b_frag[4][2];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row_l = m_tile * 16 + (lane >> 4) * 4 + r;
-      half_lse[vhalf * 64 + row_l] = m_run[r] + __logf(fmaxf(l_run[r], 1e-30f));
-      half_tgt[vhalf * 64 + row_l] = tgt[r];
-      half_lbf[vhalf * 64 + row_l] =
-          m_run[r] + __logf(fmaxf(l_run[r] + lb_run[r], 1e-30f));
-    }
-  }
-  __syncthreads();
-  if (vhalf == 0 && (lane & 15) == 0) {
+    for (int p = 0; p < 4; ++p) {
+      bf16x8 a_frag[2][2];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row_l = m_tile * 16 + (lane >> 4) * 4 + r;
-      const int row_g = t0 + row_l;
-      if (row_g < T) {
-        const float a = half_lse[row_l];
-        const float b = half_lse[64 + row_l];
-        const float mx = fmaxf(a, b);
-        lse_out[row_g] = mx + __logf(
-            __builtin_amdgcn_exp2f((a - mx) * kLog2eC) +
-            __builtin_amdgcn_exp2f((b - mx) * kLog2eC));
-        tgt_out[row_g] = fmaxf(half_tgt[row_l], half_tgt[64 + row_l]);
-        const float ab = half_lbf[row_l];
-        const float bb = half_lbf[64 + row_l];
-        const float mb = fmaxf(ab, bb);
-        lse_bf_out[row_g] = mb + __logf(
-            __builtin_amdgcn_exp2f((ab - mb) * kLog2eC) +
-            __builtin_amdgcn_exp2f((bb - mb) * kLog2eC));
+      for (int ks = 0; ks < 2; ++ks) {
+        const int kk = ks * 32 + (lane >> 4) * 8;
+#pragma unroll
+        for (int il = 0; il < 2; ++il) {
+          const int row = wm * 128 + (2 * p + il) * 16 + (lane & 15);
+          a_frag[il][ks] = lds_frag(a_base, row, kk, row);
+        }
+        if (p == 0) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            b_frag[j][ks] = Tile8BNK<256>::frag(b_base, kk, wn * 64 + j * 16, lane);
+        }
       }
+      // stage upcoming tiles into dead rows
+      if (p == 0) {
+        if (it + 1 < n_it) stage_a(it + 1, kt1, 0);
+      } else if (p == 1) {
+        if (it + 1 < n_it) stage_a(it + 1, kt1, 1);
+        if (it + 2 < n_it) { stage_b(it + 2, vt2, kt2, 0); stage_b(it + 2, vt2, kt2, 1); }
+      } else if (p == 2) {
+        if (it + 2 < n_it) { stage_b(it + 2, vt2, kt2, 2); stage_b(it + 2, vt2, kt2, 3); }
+      }
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int il = 0; il < 2; ++il)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks)
+            acc[2 * p + il][j] =
+                mfma16(a_frag[il][ks], b_frag[j][ks], acc[2 * p + il][j]);
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_barrier();
     }
+
+    if (kt0 == n_ktiles - 1) epilogue(vt0);
+    vt0 = vt1; kt0 = kt1;
+    vt1 = vt2; kt1 = kt2;
+    advance(vt2, kt2);
   }
+
+  // The four column quarters of a row, merged in quarter order.
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < kFwdTile && row0 + t < T) {
+    float m = st_m[t];
+#pragma unroll
+    for (int q = 1; q < 4; ++q) m = fmaxf(m, st_m[q * kFwdTile + t]);
+    float l = 0.f, lb = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float w =
+          __builtin_amdgcn_exp2f((st_m[q * kFwdTile + t] - m) * kLog2eC);
+      l += st_l[q * kFwdTile + t] * w;
+      lb += st_lb[q * kFwdTile + t] * w;
+    }
+    const size_t plane = (size_t)n_spans * T;
+    float* out = ws + (size_t)span * T + row0 + t;
+    out[0] = m;
+    out[plane] = l;
+    out[2 * plane] = lb;
+    out[3 * plane] = tgt_lds[t];
+  }
+}
+
+// lse, target logit and rounded lse of a row from its spans' partials, in
+// span order.
+__global__ __launch_bounds__(256) void cce_fwd_merge_kernel(
+    const float* __restrict__ ws,    // (4, n_spans, T)
+    float* __restrict__ lse_out,     // (T,)
+    float* __restrict__ tgt_out,     // (T,) target logit, -1e30 without one
+    float* __restrict__ lse_bf_out,  // (T,) lse of the bf16-ROUNDED logits
+    int T, int n_spans) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= T) return;
+  const size_t plane = (size_t)n_spans * T;
+  float m = -1e30f;
+  for (int s = 0; s < n_spans; ++s) m = fmaxf(m, ws[(size_t)s * T + row]);
+  float l = 0.f, lb = 0.f, tg = -1e30f;
+  for (int s = 0; s < n_spans; ++s) {
+    const float* p = ws + (size_t)s * T + row;
+    const float w = __builtin_amdgcn_exp2f((p[0] - m) * kLog2eC);
+    l += p[plane] * w;
+    lb += p[2 * plane] * w;
+    tg = fmaxf(tg, p[3 * plane]);
+  }
+  lse_out[row] = m + __logf(fmaxf(l, 1e-30f));
+  tgt_out[row] = tg;
+  lse_bf_out[row] = m + __logf(fmaxf(l + lb, 1e-30f));
 }
 
 }  // namespace d9d
 
+// n_spans: into how many spans of vocab tiles a row tile's sweep is cut (one
+// block each); 0 chooses, and any value is capped at the number of tiles.
 std::vector<torch::Tensor> cce_fwd(
-    torch::Tensor e, torch::Tensor c, torch::Tensor targets) {
-  TORCH_CHECK(e.is_cuda() && e.scalar_type() == torch::kBFloat16 && e.is_contiguous());
-  TORCH_CHECK(c.scalar_type() == torch::kBFloat16 && c.is_contiguous());
-  TORCH_CHECK(targets.scalar_type() == torch::kInt64);
-  const int T = e.size(0), K = e.size(1), V = c.size(0);
-  TORCH_CHECK(K % 64 == 0, "cce_fwd requires hidden % 64 == 0");
-  const bool wide = (K % 128 == 0) &&
-      (size_t)(64 * K + 128 * 128) * sizeof(__bf16) <= 160 * 1024;
-  const size_t smem =
-      (size_t)(64 * K + 128 * (wide ? 128 : 64)) * sizeof(__bf16);
-  TORCH_CHECK(smem <= 160 * 1024, "cce_fwd: hidden too large for LDS: ", K);
+    torch::Tensor e, torch::Tensor c, torch::Tensor targets, int64_t n_spans) {
+  TORCH_CHECK(e.is_cuda() && e.scalar_type() == torch::kBFloat16 &&
+              e.dim() == 2 && e.is_contiguous());
+  TORCH_CHECK(c.is_cuda() && c.scalar_type() == torch::kBFloat16 &&
+              c.dim() == 2 && c.is_contiguous());
+  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == torch::kInt64);
+  const int64_t T = e.size(0), K = e.size(1), V = c.size(0);
+  TORCH_CHECK(c.size(1) == K, "cce_fwd: c must be (V, ", K, ")");
+  TORCH_CHECK(targets.numel() == T, "cce_fwd: one target per row of e");
+  TORCH_CHECK(K % 64 == 0 && K >= 64, "cce_fwd requires hidden % 64 == 0");
+  TORCH_CHECK(V >= 1, "cce_fwd: empty classifier");
+  TORCH_CHECK(n_spans >= 0, "cce_fwd: n_spans must be >= 0, got ", n_spans);
+  TORCH_CHECK(T < (1 << 30) && V < (1 << 30), "cce_fwd: T or V too large");
 
   auto lse = torch::empty({T}, e.options().dtype(torch::kFloat32));
   auto tgt = torch::empty({T}, e.options().dtype(torch::kFloat32));
   auto lse_bf = torch::empty({T}, e.options().dtype(torch::kFloat32));
   if (T == 0) return {lse, tgt, lse_bf};
+
+  const int64_t n_rt = (T + d9d::kFwdTile - 1) / d9d::kFwdTile;
+  const int64_t n_vt = (V + d9d::kFwdTile - 1) / d9d::kFwdTile;
+  // about four rounds of the 256 CUs (one block per CU)
+  if (n_spans == 0) n_spans = std::max<int64_t>(1, 1024 / n_rt);
+  n_spans = std::min(n_spans, n_vt);
+  auto ws = torch::empty({4, n_spans, T}, e.options().dtype(torch::kFloat32));
+
+  static const bool attr_set = [] {
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&d9d::cce_fwd_tiled_kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize, d9d::kFwdLds);
+    return true;
+  }();
+  (void)attr_set;
   auto stream = at::hip::getCurrentHIPStream();
   auto tgts = targets.contiguous();
-#define LAUNCH_CCE(KT)                                                        \
-  hipLaunchKernelGGL(d9d::cce_fwd_kernel<KT>, dim3((T + 63) / 64), dim3(512), \
-                     smem, stream,                                            \
-                     reinterpret_cast<const __bf16*>(e.data_ptr()),           \
-                     reinterpret_cast<const __bf16*>(c.data_ptr()),           \
-                     tgts.data_ptr<int64_t>(), lse.data_ptr<float>(),         \
-                     tgt.data_ptr<float>(), lse_bf.data_ptr<float>(), T, V, K)
-  if (wide) LAUNCH_CCE(128); else LAUNCH_CCE(64);
-#undef LAUNCH_CCE
+  hipLaunchKernelGGL(d9d::cce_fwd_tiled_kernel, dim3((unsigned)(n_rt * n_spans)),
+                     dim3(512), d9d::kFwdLds, stream,
+                     reinterpret_cast<const __bf16*>(e.data_ptr()),
+                     reinterpret_cast<const __bf16*>(c.data_ptr()),
+                     tgts.data_ptr<int64_t>(), ws.data_ptr<float>(), (int)T,
+                     (int)V, (int)K, (int)n_rt, (int)n_spans);
+  hipLaunchKernelGGL(d9d::cce_fwd_merge_kernel, dim3((unsigned)((T + 255) / 256)),
+                     dim3(256), 0, stream, ws.data_ptr<float>(),
+                     lse.data_ptr<float>(), tgt.data_ptr<float>(),
+                     lse_bf.data_ptr<float>(), (int)T, (int)n_spans);
   return {lse, tgt, lse_bf};
 }
 

@@ -33,6 +33,7 @@
 // fallbacks stage through registers (T14) and take any K and N.
 #include "common.h"
 #include "mfma.h"
+#include "glds_tile.h"
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -45,8 +46,7 @@
 namespace d9d {
 
 constexpr int kBM = 256;
-constexpr int kBN = 192;
-constexpr int kBK = 64;
+constexpr int kBN = 192;  // kBK = 64 comes from glds_tile.h
 
 // ---- helpers shared by the kernels below ------------------------------------
 
@@ -98,14 +98,6 @@ D9D_DEVICE void store_acc_tile(bf16_t* __restrict__ out, int ld,
   }
 }
 
-// MFMA fragment (8 k-contiguous bf16 at column kk of `row`) from a
-// [rows][kBK] LDS tile whose 16-byte units are XOR-swizzled by key & 7
-// (key = row gives the plain conflict-free ds_read_b128 layout).
-D9D_DEVICE bf16x8 lds_frag(const char* tile, int row, int kk, int key) {
-  const int byte = (kk * 2) ^ ((key & 7) << 4);
-  return *reinterpret_cast<const bf16x8*>(tile + row * (kBK * 2) + byte);
-}
-
 // MFMA fragment from a ROW-major operand staged as a [red/4][W/16][4][16]
 // blocked image (red = reduction dim, W = tile width): reduction slice
 // red0..red0+8 at the 16 columns of column block ct. ds_read_b64_tr_b16
@@ -125,14 +117,6 @@ D9D_DEVICE bf16x8 tr16_frag(const char* img, int W, int red0, int ct, int lane) 
 #pragma unroll
   for (int t = 0; t < 4; ++t) { f[t] = lo4[t]; f[4 + t] = hi4[t]; }
   return f;
-}
-
-// Async 16-byte global -> LDS copy (global_load_lds_dwordx4): no staging
-// register, no ds_write; completion is counted by vmcnt. It cannot mask,
-// so every source address must be in bounds.
-D9D_DEVICE void glds16(const char* src, char* dst) {
-  __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t*>(src),
-                                   reinterpret_cast<uint32_t*>(dst), 16, 0, 0);
 }
 
 // ---- register-staged forward/dgrad fallback (any K, any N) ------------------
@@ -370,27 +354,7 @@ __global__ __launch_bounds__(512, 1) void gmm_staged_kernel(
 // `chunk` of the k-tile starting at k0 into the slot's B region, and frag()
 // reads the MFMA B-fragment for k offset kk at the 16 tile columns from col0.
 
-// B stored (E, N, K): rows are k-contiguous like A's, so the B region is a
-// [BN8][kBK] row-major tile with A's swizzle, produced by PRE-SWIZZLING the
-// per-lane global source address (glds writes linearly: wave-uniform base +
-// lane*16). A chunk is 64 rows.
-template <int BN8>
-struct Tile8BNK {
-  static D9D_DEVICE void stage(const bf16_t* __restrict__ w_e, char* b_slot,
-                               int k0, int n0, int K, int N, int chunk,
-                               int wave, int lane) {
-    const int l = wave * 1024 + lane * 16;
-    const int nrow = chunk * 64 + (l >> 7);
-    const int colb = (l & 127) ^ ((nrow & 7) << 4);
-    const int64_t sn = min(n0 + nrow, N - 1);
-    glds16(reinterpret_cast<const char*>(w_e) + (sn * (int64_t)K + k0) * 2 + colb,
-           b_slot + chunk * (8 * 1024) + l);
-  }
-  static D9D_DEVICE bf16x8 frag(const char* b_slot, int kk, int col0, int lane) {
-    const int col = col0 + (lane & 15);
-    return lds_frag(b_slot, col, kk, col);
-  }
-};
+// B stored (E, N, K): Tile8BNK, glds_tile.h.
 
 // B stored (E, K, N), n-contiguous rows (dgrad: out = g @ w[e]): the MFMA
 // fragment needs 8 reduction (k) elements at fixed n — a COLUMN of the
